@@ -19,9 +19,18 @@ Launch: `python3 bench.py --gpus N` starts its N rank processes itself (before
 anything touches the GPU; launch_ranks), or runs as one rank under
 torch.distributed.run (RANK / WORLD_SIZE / MASTER_* set by the launcher).
 
+A plain run does what the headline needs and no more: set-up, warmup, the timed
+steps, the JSON line (with the per-kernel and roofline figures that the warmup
+and the timed steps themselves yield).  `--full` adds every other measurement:
+the cpu_baseline leg, the two-bucket side line and allreduce_p1 (N = 1), and
+the N > 1 line's side lines, roofline pass and wall budget.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy
+(float32; a fixed seeded sample of a large array), so two builds can be compared
+output for output: the inputs are seeded and the same from run to run.
+
 Every byte is produced by the gfx950 kernels through the C ABI
 (bagua-core_amd/lib/*.so).  The oracle is used ONLY for the cpu_baseline leg
-(rank 0, N = 1): the C restatement of the reference kernels timed on the
+(rank 0, --full): the C restatement of the reference kernels timed on the
 host's cores on a bounded sample.
 """
 from __future__ import annotations
@@ -177,6 +186,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the CPU baseline, the two-bucket side line, "
+                         "allreduce_p1 (N = 1), and the N > 1 line's side lines and roofline pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of an array above 2^22 elements)")
     ap.add_argument("--workload", choices=["auto", "codec", "allreduce", "onebit", "host", "backend"], default="auto")
     ap.add_argument("--buckets", type=int, default=32, help="backend workload: gradient buckets per iteration")
     ap.add_argument("--bucket-mib", type=int, default=25, help="backend workload: MiB of fp32 gradient per bucket")
@@ -252,6 +267,25 @@ def pmc_traffic(kernel: str, summary: str = PMC_SUMMARY):
         return d.get("per_launch_hbm_bytes", {}).get(kernel)
     except (OSError, ValueError):
         return None
+
+
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: elements written per array (16 MiB of float32)
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: every array as dirname/<name>.npy in float32 (u8, f16 and bf16 values are
+    exact in it).  An array above DUMP_SAMPLE elements is written as its first 64 elements
+    (a payload's header) followed by a sample at fixed positions (numpy PCG64, seed 0x5EED,
+    ascending), the same positions in every run and build."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(0x5EED).integers(64, t.numel(), DUMP_SAMPLE - 64))
+            pos = np.concatenate([np.arange(64), pos])
+            t = t[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.to(torch.float32).cpu().numpy())
 
 
 # ----------------------------------------------------------------- N = 1 ------
@@ -383,6 +417,8 @@ def bench_codec(args, onebit: bool = False):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     gu_timed = give_ups() - gu0 if resident else None
+    if args.dump_outputs:  # what a caller of the step receives: the payload and the decoded bucket
+        dump_outputs(args.dump_outputs, {"compressed": comp, "decoded": y})
     ms = wall * 1e3 / args.steps
     value = esz * n / (ms * 1e-3) / GiB  # gradient bytes processed (4N fp32, 2N bf16)
     dom_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
@@ -420,8 +456,8 @@ def bench_codec(args, onebit: bool = False):
     }
     # Side line: the same steps alternating between two buckets, so each step's bucket
     # was last touched a whole other bucket ago (>= 2 x 256 MiB of traffic since: no
-    # Infinity-Cache reuse across steps, which the one-bucket loop may enjoy)
-    if not args.no_cold:
+    # Infinity-Cache reuse across steps, which the one-bucket loop may enjoy); --full only
+    if args.full and not args.no_cold:
         x2 = (torch.randn(n, device=dev, generator=g) * 1e-3).to(tdt)
         y2, comp2 = torch.empty_like(y), torch.empty_like(comp)
         torch.cuda.synchronize()  # x2 was generated on the current stream
@@ -541,22 +577,27 @@ def bench_host(args):
         torch.cuda.synchronize()
         return 4.0 * n / ((time.perf_counter() - t0) / steps) / GiB
 
-    serial(max(1, args.warmup))
+    if args.full:  # beside the headline: the four steps back to back per bucket
+        serial(max(1, args.warmup))
     overlapped(max(2, args.warmup))
-    t_ser = serial(args.steps)
+    t_ser = serial(args.steps) if args.full else None
     t_ovl = overlapped(args.steps)
     torch.cuda.synchronize()
     ok = torch.equal(dst[(args.steps - 1) % nb], y[(args.steps - 1) % nb].cpu())
+    if args.dump_outputs:  # the last bucket's payload and the decoded bucket copied back to the host
+        dump_outputs(args.dump_outputs, {"compressed": comp[(args.steps - 1) % nb],
+                                         "decoded": dst[(args.steps - 1) % nb]})
     value = 4.0 * n / t_ovl / GiB
     cfg = {"workload": f"minmax_uint8_encode_decode_{4 * n >> 20}MiB_fp32_bucket_host_resident", "bucket_elements": n,
            "n_chunks": 1, "config_index": 2, "buffers": "pinned host fp32 in/out", "copy_pieces": chunks,
            "buckets_in_flight": nb}
-    extra = {"serial_gib_s": round(4.0 * n / t_ser / GiB, 2), "serial_ms_per_bucket": round(t_ser * 1e3, 3),
-             "overlapped_gib_s": round(value, 2), "h2d_gib_s": round(copy_rate(True, 5), 2),
-             "d2h_gib_s": round(copy_rate(False, 5), 2), "result_copied_back_intact": bool(ok)}
-    x[0].copy_(src)
-    codec(0, torch.cuda.current_stream(dev))
-    torch.cuda.synchronize()
+    extra = {"overlapped_gib_s": round(value, 2), "result_copied_back_intact": bool(ok)}
+    if args.full:
+        extra.update({"serial_gib_s": round(4.0 * n / t_ser / GiB, 2), "serial_ms_per_bucket": round(t_ser * 1e3, 3),
+                      "h2d_gib_s": round(copy_rate(True, 5), 2), "d2h_gib_s": round(copy_rate(False, 5), 2)})
+        x[0].copy_(src)  # the bucket and payload the cpu_baseline leg compares with
+        codec(0, torch.cuda.current_stream(dev))
+        torch.cuda.synchronize()
     return value, t_ovl * 1e3, None, cfg, extra, (x[0], comp[0])
 
 
@@ -994,6 +1035,19 @@ def bench_allreduce(args, world: int, rank: int, local_rank: int):
         args.pieces = 1
         t_c = timed(lambda: compressed_step(1), args.steps, args.warmup)
     PHASES.lap("headline")
+    if args.dump_outputs and rank == 0:  # the op works in place: the bucket after the last timed step
+        dump_outputs(args.dump_outputs, {"reduced": x})
+    cfg = {"workload": f"minmax_uint8_compressed_allreduce_{4 * n >> 20}MiB_fp32_per_rank", "bucket_elements": n,
+           "n_chunks": world, "collectives": "rccl alltoall + allgather (uint8)", "parallelism": f"dp{world}",
+           "config_index": 4}
+    if not args.full:  # a plain run: the headline alone
+        extra = {"per_rank_gib_s": round(4.0 * n / t_c / GiB, 2), "pieces": args.pieces or "auto",
+                 "pieces_tapered": headline_taper[0],
+                 "pieces_autotune_ms_per_step": {q: round(v * 1e3, 3) for q, v in autotune.items()} or None}
+        if headline_fallback:
+            extra["headline_fallback"] = headline_fallback
+        del comm
+        return world * 4.0 * n / t_c / GiB, t_c * 1e3, None, cfg, extra
     # What the north star compares the headline with, measured right after it (never
     # skipped for the budget): the uncompressed fp32 RCCL all-reduce of the same bucket,
     # and the op's two collectives alone on its compressed bytes (RCCL alltoall of S
@@ -1151,9 +1205,6 @@ def bench_allreduce(args, world: int, rank: int, local_rank: int):
             "traffic": pmc_traffic(names[dom]) if n == (1 << 26) and world == 1 else None,
             "alg_bytes_per_launch": alg[dom], "avg_launch_us": round(per[dom] * 1e3, 2)}
     PHASES.lap("roofline")
-    cfg = {"workload": f"minmax_uint8_compressed_allreduce_{4 * n >> 20}MiB_fp32_per_rank", "bucket_elements": n,
-           "n_chunks": world, "collectives": "rccl alltoall + allgather (uint8)", "parallelism": f"dp{world}",
-           "config_index": 4}
     extra = {"per_rank_gib_s": round(per_rank, 2), "fp32_allreduce_gib_s": round(fp32, 2),
              "ratio_vs_fp32": round(per_rank / fp32, 3), "fp32_ms_per_step": round(t_f * 1e3, 3),
              "pieces": args.pieces or "auto",
@@ -1276,11 +1327,12 @@ def bench_backend(args, world: int, rank: int, local_rank: int):
     barrier = (lambda: dist.barrier()) if world > 1 else None
     lanes = args.lanes or wl.backend.lanes()
     # one lane first, the configured lanes last (a kernel trace's tail is the headline's)
-    ms1 = wl.time(args.steps, args.warmup, 1, barrier) if lanes != 1 else None
+    ms1 = wl.time(args.steps, args.warmup, 1, barrier) if (args.full and lanes != 1) else None
     wl.mark_s.clear()
     ms = wl.time(args.steps, args.warmup, lanes, barrier)
     mark = sorted(wl.mark_s)[len(wl.mark_s) // 2]
-    ms1 = ms if ms1 is None else ms1
+    if args.dump_outputs and rank == 0:  # the ops work in place: every bucket after the last iteration
+        dump_outputs(args.dump_outputs, {"reduced": torch.cat(wl.flats)})
     grad_bytes = 4.0 * wl.per * args.buckets
     value = world * grad_bytes / (ms * 1e-3) / GiB
     cfg = {"workload": f"comm_backend_{args.buckets}x{args.bucket_mib}MiB_fp32_buckets_minmax_uint8",
@@ -1289,9 +1341,11 @@ def bench_backend(args, world: int, rank: int, local_rank: int):
     extra = {"per_bucket_us": round(ms * 1e3 / args.buckets, 2), "per_rank_gib_s": round(value / world, 2),
              # host time of the Python side per bucket (a ready event + one mark per tensor): the
              # scheduler cannot run a bucket before its last tensor is marked
-             "mark_us_per_bucket": round(mark * 1e6 / args.buckets, 2),
-             "one_lane": {"ms_per_step": round(ms1, 4), "per_bucket_us": round(ms1 * 1e3 / args.buckets, 2),
-                          "gib_s_total": round(world * grad_bytes / (ms1 * 1e-3) / GiB, 2)}}
+             "mark_us_per_bucket": round(mark * 1e6 / args.buckets, 2)}
+    if args.full:  # beside the configured lanes: the same iterations on one lane
+        ms1 = ms if ms1 is None else ms1
+        extra["one_lane"] = {"ms_per_step": round(ms1, 4), "per_bucket_us": round(ms1 * 1e3 / args.buckets, 2),
+                             "gib_s_total": round(world * grad_bytes / (ms1 * 1e-3) / GiB, 2)}
     wl.close()
     del comm
     return value, ms, None, cfg, extra
@@ -1326,13 +1380,14 @@ def main():
     cpu = None
     if workload in ("codec", "onebit"):
         value, ms, roof, cfg, extra, (xb, cb) = bench_codec(args, onebit=(workload == "onebit"))
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and args.full and not args.no_cpu_baseline:
             try:
                 cpu = cpu_codec_baseline(args, xb, cb, onebit=(workload == "onebit"))
             except Exception as e:  # noqa: BLE001 - a failed baseline must not lose the headline line
                 cpu = {"error": str(e)[:200]}
         del xb, cb
-        if args.workload == "auto" and world == 1 and not args.no_allreduce_p1 and not args.elements:
+        if (args.full and args.workload == "auto" and world == 1 and not args.no_allreduce_p1
+                and not args.elements):
             # the default line: config 2 (headline) + config 4 at one rank (the 1 -> 8 GPU curve's N = 1 point)
             try:
                 extra["allreduce_p1"] = allreduce_p1(args)
@@ -1341,7 +1396,7 @@ def main():
         dtype = f"{args.dtype} -> u8" if workload == "codec" else f"{args.dtype} -> 1bit"
     elif workload == "host":
         value, ms, roof, cfg, extra, (xb, cb) = bench_host(args)
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and args.full and not args.no_cpu_baseline:
             try:
                 cpu = cpu_codec_baseline(args, xb, cb)
             except Exception as e:  # noqa: BLE001 - a failed baseline must not lose the headline line
@@ -1357,7 +1412,7 @@ def main():
             n_cpu = cfg["bucket_elements"]
         # after every rank's timed region: rank 0 times the op on the host cores while
         # the others wait at the closing barrier
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and args.full and not args.no_cpu_baseline:
             if workload == "allreduce" and world > 1:  # inside the line's wall budget too
                 left = args.budget_s - (time.perf_counter() - _PROCESS_T0)
                 args.cpu_seconds = max(0.5, min(args.cpu_seconds, left - 10.0))

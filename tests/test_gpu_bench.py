@@ -1,8 +1,9 @@
 """The bench.py contract the driver reads: ONE strict-JSON line on stdout with
 the metric, the whole-job value, the roofline of the dominant kernel and the
-CPU baseline (N = 1), for the default run and the other workloads.  Short
+CPU baseline (N = 1, --full), for the default run and the other workloads.  Short
 runs (a few steps) in a child process; the numbers themselves are not checked
-here, only that they are present, finite and consistent with each other."""
+here, only that they are present, finite and consistent with each other.  A
+plain run (no --full) carries the headline alone and can write its outputs."""
 import json
 import math
 import os
@@ -41,12 +42,12 @@ def check_common(d, steps, warmup):
 
 @pytest.fixture(scope="module")
 def default_line():
-    return run_bench("--steps", "20", "--warmup", "3", "--cpu-seconds", "0.5")
+    return run_bench("--full", "--steps", "20", "--warmup", "3", "--cpu-seconds", "0.5")
 
 
 @pytest.fixture(scope="module")
 def allreduce_line():
-    return run_bench("--workload", "allreduce", "--steps", "20", "--warmup", "3", "--cpu-seconds", "0.5",
+    return run_bench("--full", "--workload", "allreduce", "--steps", "20", "--warmup", "3", "--cpu-seconds", "0.5",
                      "--no-decentralized", timeout=200)
 
 
@@ -73,8 +74,31 @@ def check_cpu(d):
     assert d["hw_queues"]["effective"] == d["hw_queues"]["inherited"]  # N = 1 leaves the setting alone
 
 
+def test_plain_run_is_the_headline_alone_and_dumps_outputs(tmp_path, default_line):
+    """Without --full: the same headline line, none of the side measurements; --dump-outputs
+    writes the last step's payload and decoded bucket as float32 samples (first 64 elements,
+    then fixed seeded positions), bounded in size, and the payload's header (MinMax-UInt8:
+    min and max as fp32 in the first 8 bytes) brackets every decoded value."""
+    import numpy as np
+    d = run_bench("--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path / "out"))
+    check_common(d, 4, 2)
+    assert d["config"] == default_line["config"] and d["dtype"] == default_line["dtype"] == "f32 -> u8"
+    assert abs(d["value"] - 256 / 1024 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+    assert d["cpu_baseline"] is None and "allreduce_p1" not in d and "two_bucket_alternating" not in d
+    assert "two_bucket_alternating" in default_line
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["compressed.npy", "decoded.npy"]
+    comp, dec = (np.load(tmp_path / "out" / f) for f in files)
+    assert comp.dtype == dec.dtype == np.float32 and comp.shape == dec.shape == (1 << 22,)
+    assert comp.nbytes + dec.nbytes <= 64 << 20
+    assert np.array_equal(comp, np.rint(comp)) and comp.min() >= 0 and comp.max() <= 255  # bytes, exactly
+    lo, hi = comp[:8].astype(np.uint8).view(np.float32)
+    assert lo < 0 < hi and dec.min() >= lo - (hi - lo) / 255 and dec.max() <= hi + (hi - lo) / 255
+    assert np.unique(dec).size > 200  # the decoded sample spans the 256 levels
+
+
 def test_onebit_run():
-    d = run_bench("--workload", "onebit", "--steps", "5", "--warmup", "2", "--cpu-seconds", "0.5")
+    d = run_bench("--full", "--workload", "onebit", "--steps", "5", "--warmup", "2", "--cpu-seconds", "0.5")
     check_common(d, 5, 2)
     assert d["config"]["config_index"] == 3
     assert d["roofline"]["kernel"] == "onebit_encode_kernel"

@@ -168,7 +168,7 @@ def test_bench_side_line_timeout_recovers(tmp_path):
     env.update({"BAGUA_BENCH_SHARED_GPU": "1", "NCCL_IB_DISABLE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0",
                 "BAGUA_BENCH_FAIL_SIDE": "scheduler_lanes3"})
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--elements", str(1 << 22), "--cpu-seconds", "1"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -198,7 +198,7 @@ def test_bench_line_budget(tmp_path):
     env.update({"BAGUA_BENCH_SHARED_GPU": "1", "NCCL_IB_DISABLE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0",
                 "BAGUA_BENCH_SPEND": "unpieced:60"})
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--elements", str(1 << 22), "--cpu-seconds", "1", "--budget-s", "60"]
     t0 = time.time()
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
@@ -222,7 +222,7 @@ def test_bench_line_zero_budget(tmp_path):
     env = dict(os.environ)
     env.update({"BAGUA_BENCH_SHARED_GPU": "1", "NCCL_IB_DISABLE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--elements", str(1 << 22), "--cpu-seconds", "1", "--budget-s", "0"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -248,7 +248,8 @@ def test_bench_line_multirank(tmp_path, world, fail_headline, launcher):
     env.update({"BAGUA_BENCH_SHARED_GPU": "1", "NCCL_IB_DISABLE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     if fail_headline:
         env["BAGUA_BENCH_FAIL_HEADLINE"] = "1"
-    args = ["--gpus", str(world), "--steps", "3", "--warmup", "1", "--elements", str(1 << 22), "--cpu-seconds", "1"]
+    args = ["--full", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--elements", str(1 << 22),
+            "--cpu-seconds", "1"]
     if launcher == "self":
         env.pop("WORLD_SIZE", None)
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args
@@ -291,6 +292,35 @@ def test_bench_line_multirank(tmp_path, world, fail_headline, launcher):
     for k in ("startup", "setup", "headline", "fp32_allreduce", "scheduler_buckets", "onebit", "cpu_baseline"):
         assert ph[k] >= 0, (k, ph)
     assert abs(ph["unaccounted"]) <= 0.05 * ph["process_wall"], ph
+
+
+def test_bench_plain_line_multirank(tmp_path):
+    """Without --full the N > 1 line is setup -> piece autotune -> headline and nothing else:
+    no side line, no roofline pass, no CPU baseline; --dump-outputs writes rank 0's bucket as
+    the last timed step left it (every rank ends an all-reduce with the same values)."""
+    import json
+    env = dict(os.environ)
+    env.update({"BAGUA_BENCH_SHARED_GPU": "1", "NCCL_IB_DISABLE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
+    env.pop("WORLD_SIZE", None)
+    n = 1 << 22
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--elements", str(n), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["config"]["config_index"] == 4 and d["dtype"] == "f32 -> u8"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 2 * 4 * n / (d["ms_per_step"] * 1e-3) / 2**30) < 0.01 * d["value"]
+    assert set(d["pieces_autotune_ms_per_step"]) == {"1", "2", "4", "8", "16", "4_tapered", "8_tapered"}, d
+    assert "headline_fallback" not in d and d["cpu_baseline"] is None and d["roofline"] is None, d
+    for k in ("fp32_allreduce_gib_s", "comm_only_ms", "onebit_allreduce", "bucket_25mib", "decentralized_bf16",
+              "scheduler_buckets", "pieces_sweep_ms_per_step", "side_errors"):
+        assert k not in d, k
+    assert set(d["phase_wall_s"]) == {"startup", "setup", "autotune", "headline", "unaccounted", "process_wall"}
+    assert os.listdir(tmp_path / "out") == ["reduced.npy"]
+    x = np.load(tmp_path / "out" / "reduced.npy")
+    assert x.dtype == np.float32 and x.shape == (n,) and np.isfinite(x).all() and np.unique(x).size > 200
 
 
 def test_native_scheduler(tmp_path, oracle_c):
