@@ -53,11 +53,14 @@ class bagua_bucket_op_t(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("average", ctypes.c_int32), ("compression", ctypes.c_int32),
                 ("fused", ctypes.c_int32), ("comm", ctypes.c_void_p), ("weight", bagua_tensor_t),
                 ("left_peer_weight", bagua_tensor_t), ("right_peer_weight", bagua_tensor_t),
-                ("callback", ctypes.c_void_p), ("user", ctypes.c_void_p), ("intranode", ctypes.c_void_p)]
+                ("callback", ctypes.c_void_p), ("user", ctypes.c_void_p), ("intranode", ctypes.c_void_p),
+                ("ef_worker_carry", bagua_tensor_t), ("ef_worker_scales", bagua_tensor_t),
+                ("ef_server_carry", bagua_tensor_t), ("ef_server_scale", bagua_tensor_t)]
 
 
 BUCKET_OP_CENTRALIZED_LOW_PRECISION, BUCKET_OP_CENTRALIZED_FULL_PRECISION = 1, 2
 BUCKET_OP_DECENTRALIZED_LOW_PRECISION, BUCKET_OP_CALLBACK = 3, 4
+BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK = 5
 STATUS_INVALID_ARG = 1
 
 _T = ctypes.POINTER(bagua_tensor_t)
@@ -124,6 +127,13 @@ KERNEL_SIGNATURES = {
     "bagua_onebit_encode_range": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _vp, _sz, _i32, _i32, _vp]),
     "bagua_onebit_finalize": (_i32, [_vp, _sz, _i32, _i32, _i32, _vp, _sz, _vp]),
     "bagua_onebit_decompress_range": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "bagua_onebit_ef_state_bytes": (_i32, [_i32, _i32, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "bagua_onebit_compress_ef": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _vp, _sz, _i32, _vp, _vp, _vp]),
+    "bagua_onebit_encode_range_ef": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _vp, _sz, _i32, _i32, _vp, _vp,
+                                            _vp]),
+    "bagua_onebit_finalize_ef": (_i32, [_vp, _sz, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
+    "bagua_onebit_reduce_requantize_ef": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _sz, _vp,
+                                                 _vp, _vp]),
     "bagua_reduce_chunks": (_i32, [_i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "bagua_add_inplace": (_i32, [_i32, _vp, _vp, _i32, _vp]),
     "bagua_addmul_inplace": (_i32, [_i32, _vp, _vp, _i32, _f32, _vp]),
@@ -173,6 +183,7 @@ CORE_SIGNATURES = {
     "bagua_compressed_size": (_sz, [_i32, _i32, _sz, _sz]),
     "bagua_tensor_compress": (_i32, [_T, _i32, _i32, _u64, _i32, _T]),
     "bagua_tensor_compress_into": (_i32, [_T, _i32, _i32, _u64, _i32, _T]),
+    "bagua_tensor_compress_error_feedback": (_i32, [_T, _i32, _u64, _T, _T, _T]),
     "bagua_tensor_decompress_from": (_i32, [_T, _i32, _i32, _T, _u64]),
     "bagua_tensor_reduce_inplace": (_i32, [_T, _i32, _i32, _i32, _u64]),
     "bagua_tensor_add_inplace": (_i32, [_T, _T, _u64]),
@@ -211,6 +222,7 @@ CORE_SIGNATURES = {
     "bagua_centralized_low_precision_synchronous": (_i32, [_C, _T, _i32, _i32]),
     "bagua_centralized_low_precision_synchronous_unfused": (_i32, [_C, _T, _i32, _i32]),
     "bagua_centralized_low_precision_pipelined": (_i32, [_C, _T, _i32, _i32, _i32]),
+    "bagua_centralized_onebit_error_feedback": (_i32, [_C, _T, _i32, _T, _T, _T, _T, _i32]),
     "bagua_centralized_full_precision_synchronous": (_i32, [_C, _T, _i32]),
     "bagua_decentralized_low_precision_synchronous": (_i32, [_C, _T, _T, _T, _T, _i32]),
     "bagua_decentralized_low_precision_synchronous_unfused": (_i32, [_C, _T, _T, _T, _T, _i32]),

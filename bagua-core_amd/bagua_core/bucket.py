@@ -8,6 +8,7 @@ native scheduler's worker thread) runs every op through ONE C-ABI entry point
 on the communicator's stream:
 
   CentralizedLowPrecisionSynchronous   -> bagua_centralized_low_precision_synchronous
+  CentralizedOneBitErrorFeedback       -> bagua_centralized_onebit_error_feedback
   CentralizedFullPrecisionSynchronous  -> bagua_centralized_full_precision_synchronous
   DecentralizedLowPrecisionSynchronous -> bagua_decentralized_low_precision_synchronous
   PythonOp                             -> a ctypes callback (python_ffi_op.rs)
@@ -26,7 +27,7 @@ from typing import Callable, Optional
 
 from . import _native as N
 from .communicator import BaguaSingleCommunicatorPy
-from .tensor import _DTYPES, BaguaTensorPy, compression_code
+from .tensor import _DTYPES, BaguaTensorPy, OneBitErrorFeedbackState, compression_code
 
 CALLBACK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_char_p)
 
@@ -47,6 +48,25 @@ class CentralizedLowPrecisionSynchronous:
         return N.bagua_bucket_op_t(kind=N.BUCKET_OP_CENTRALIZED_LOW_PRECISION, average=int(self.average),
                                    compression=compression_code(self.compression), fused=int(self.fused),
                                    comm=_handle(self.communicator), intranode=_handle(self.intranode))
+
+
+@dataclass
+class CentralizedOneBitErrorFeedback:
+    """the "OneBitSignScale" centralized op carrying its quantisation error from step to
+    step in `state` (kept alive with the op)"""
+    communicator: BaguaSingleCommunicatorPy
+    average: bool
+    state: OneBitErrorFeedbackState
+    compression: str = "OneBitSignScale"
+
+    def native(self) -> N.bagua_bucket_op_t:
+        st = self.state
+        return N.bagua_bucket_op_t(kind=N.BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK, average=int(self.average),
+                                   compression=compression_code(self.compression), fused=1,
+                                   comm=_handle(self.communicator), ef_worker_carry=st._raw(st.worker_carry),
+                                   ef_worker_scales=st._raw(st.worker_scales),
+                                   ef_server_carry=st._raw(st.server_carry),
+                                   ef_server_scale=st._raw(st.server_scale))
 
 
 @dataclass
@@ -168,7 +188,13 @@ class BaguaBucketPy:
     def append_centralized_synchronous_op(self, communicator_internode: Optional[BaguaSingleCommunicatorPy],
                                           communicator_intranode: Optional[BaguaSingleCommunicatorPy] = None,
                                           hierarchical: bool = False, average: bool = True,
-                                          scattergather: bool = False, compression: Optional[str] = None) -> None:
+                                          scattergather: bool = False, compression: Optional[str] = None,
+                                          error_feedback: Optional[OneBitErrorFeedbackState] = None) -> None:
+        """error_feedback (keyword; "OneBitSignScale" only, not hierarchical): the state that
+        carries the op's quantisation error from one execution to the next"""
+        if error_feedback is not None:
+            self._append_error_feedback(communicator_internode, hierarchical, average, compression, error_feedback)
+            return
         comm, intra = self._communicators(communicator_internode, communicator_intranode, hierarchical)
         if compression is None:
             if scattergather:
@@ -177,6 +203,29 @@ class BaguaBucketPy:
         else:
             compression_code(compression)
             self._append(CentralizedLowPrecisionSynchronous(comm, average, compression, intranode=intra))
+
+    def _append_error_feedback(self, comm, hierarchical, average, compression, state) -> None:
+        if compression != "OneBitSignScale":
+            raise NotImplementedError(f"error feedback exists for the OneBitSignScale codec only, not for "
+                                      f"compression={compression!r}")
+        if hierarchical:
+            raise NotImplementedError("error feedback is not available in hierarchical mode")
+        if comm is None:
+            raise RuntimeError("inter node communicator must be given in non-hierarchical mode")
+        if not isinstance(state, OneBitErrorFeedbackState):
+            raise TypeError("error_feedback must be a OneBitErrorFeedbackState")
+        if state._op is not None and state._op() is not None:
+            raise RuntimeError("this error-feedback state already belongs to another op: one state, one op")
+        n = sum(t.num_elements_allocated() for t in self._tensors)
+        first = self._tensors[0].raw()
+        if (state.num_elements, state.nranks, state.device_id) != (n, comm.nranks(), first.device_id):
+            raise RuntimeError(f"{state!r} does not fit bucket {self.name}: {n} elements, {comm.nranks()} ranks, "
+                               f"device {first.device_id}")
+        if first.dtype not in (N.DTYPE_F32, N.DTYPE_F16, N.DTYPE_BF16):
+            raise RuntimeError("error feedback needs a floating-point bucket")
+        op = CentralizedOneBitErrorFeedback(comm, average, state)
+        self._append(op)
+        state._op = weakref.ref(op)
 
     def append_low_precision_decentralized_synchronous_op(
             self, communicator_internode: Optional[BaguaSingleCommunicatorPy],

@@ -174,6 +174,27 @@ class BaguaTensorPy:
         res._used_on(current_stream_ptr(src.device_id))
         return res
 
+    def compress_with_error_feedback(self, n_chunks: int, state: "OneBitErrorFeedbackState") -> "BaguaTensorPy":
+        """compress("OneBitSignScale", n_chunks, -1) of this step's compensated values
+        (DESIGN.md §4): the worker half of `state` (carry, one scale per chunk) is read and
+        updated in place; the result is the U8 buffer, owned like compress()'s."""
+        src = self.raw()
+        if n_chunks <= 0 or src.num_elem_allocated % n_chunks != 0:
+            raise RuntimeError("compression tensor size % n_chunks must be 0")
+        if state.num_elements != src.num_elem or state.nranks != n_chunks or state.device_id != src.device_id:
+            raise RuntimeError(f"error-feedback state is for {state.num_elements} elements in {state.nranks} chunks "
+                               f"on device {state.device_id}; the tensor has {src.num_elem} in {n_chunks} on "
+                               f"device {src.device_id}")
+        out = N.bagua_tensor_t()
+        stream = current_stream_ptr(src.device_id)
+        carry, scales = state._raw(state.worker_carry), state._raw(state.worker_scales)
+        rc = N.C.bagua_tensor_compress_error_feedback(ctypes.byref(src), n_chunks, stream, ctypes.byref(carry),
+                                                      ctypes.byref(scales), ctypes.byref(out))
+        N.check(rc, f"compress_with_error_feedback(n_chunks={n_chunks})")
+        res = BaguaTensorPy._from_raw(out, "compressed_tensor", owned=True)
+        res._used_on(stream)
+        return res
+
     def decompress_from(self, method: str, n_chunks: int, compressed_buffer: "BaguaTensorPy") -> None:
         code = compression_code(method)
         dst = self.raw()
@@ -227,3 +248,42 @@ class BaguaTensorPy:
         r = self.raw()
         return (f"BaguaTensorPy(name={self._name!r}, dtype={_DTYPE_NAMES[r.dtype]}, num_elements={r.num_elem}, "
                 f"device_id={r.device_id})")
+
+
+class OneBitErrorFeedbackState:
+    """The state of the 1-bit codec's error feedback for one bucket: four
+    zero-initialised float32 device tensors, ordinary torch tensors the caller may
+    checkpoint and restore.
+
+      worker_carry[num_elements], worker_scales[nranks]      what this rank encodes
+      server_carry[num_elements / nranks], server_scale[1]   the own chunk it re-encodes
+
+    The carries hold the previous step's compensated values; the residual is rebuilt
+    from them and the previous scales, so zero state means "no error carried"."""
+
+    def __init__(self, num_elements: int, nranks: int, device_id: int):
+        if nranks <= 0 or num_elements <= 0 or num_elements % nranks != 0:
+            raise ValueError(f"num_elements ({num_elements}) must be a positive multiple of nranks ({nranks})")
+        self.num_elements, self.nranks, self.device_id = int(num_elements), int(nranks), int(device_id)
+        dev = torch.device("cuda", self.device_id)
+        self.worker_carry = torch.zeros(self.num_elements, dtype=torch.float32, device=dev)
+        self.worker_scales = torch.zeros(self.nranks, dtype=torch.float32, device=dev)
+        self.server_carry = torch.zeros(self.num_elements // self.nranks, dtype=torch.float32, device=dev)
+        self.server_scale = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._op = None  # the bucket op using this state (one state, one op)
+
+    def tensors(self) -> tuple:
+        return self.worker_carry, self.worker_scales, self.server_carry, self.server_scale
+
+    def zero_(self) -> "OneBitErrorFeedbackState":
+        for t in self.tensors():
+            t.zero_()
+        return self
+
+    def _raw(self, t: torch.Tensor) -> N.bagua_tensor_t:
+        n = t.numel()
+        return N.bagua_tensor_t(t.data_ptr(), n, n, N.DTYPE_F32, self.device_id)
+
+    def __repr__(self) -> str:
+        return (f"OneBitErrorFeedbackState(num_elements={self.num_elements}, nranks={self.nranks}, "
+                f"device_id={self.device_id})")

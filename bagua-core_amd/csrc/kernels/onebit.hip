@@ -18,124 +18,9 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "codec_common.hpp"
-#include "launch_util.hpp"
+#include "onebit_common.hpp"  // tile layout, summation tree, wave helpers (shared with onebit_ef.hip)
 
 namespace bagua {
-
-constexpr int kObTile = 1024;
-constexpr int kObTileBytes = 128;
-constexpr int kObFinalizeThreads = 1024;
-// encode / decode grid caps: 64 B of loads in flight per lane (one tile per
-// iteration for 32-bit types, two for 16-bit ones).  Round 1 picked 1024 encode
-// workgroups over 2048 (profiles/r01_onebit_shape_sweep.jsonl); round 3 found
-// one tile per wave better still (16384 workgroups for 2^26 f32 elements):
-// encode 45.8 -> 43.8 us, decode 42.7 -> 42.0 us per 256 MiB
-// (tools/grid_sweep.py, profiles/r03_grid_sweep.jsonl); round 4 kept one tile per
-// wave up to 1 GiB buckets (65536 workgroups): 1 GiB encode 186 -> 176 us, decode
-// 193 -> 190 us, 256 MiB unchanged (profiles/r04_onebit_shape_sweep.jsonl)
-constexpr int kObEncodeBlocks = 65536;
-constexpr int kObDecodeBlocks = 65536;
-
-__device__ __forceinline__ int64_t ob_valid(int64_t in_num_elem, int64_t cs, int c) {
-    int64_t r = in_num_elem - (int64_t)c * cs;
-    return r < 0 ? 0 : (r < cs ? r : cs);
-}
-
-// 4 consecutive elements of T starting at p (vector load when 4*sizeof(T)-aligned)
-template <typename T>
-__device__ __forceinline__ void load4(const typename T::storage* p, int64_t j, int64_t n, bool vec, float (&f)[4]) {
-    using S = typename T::storage;
-    if (vec && j + 4 <= n) {
-        if constexpr (sizeof(S) == 4) {
-            const uint4 v = nt_load16(p + j);
-            f[0] = __uint_as_float(v.x); f[1] = __uint_as_float(v.y);
-            f[2] = __uint_as_float(v.z); f[3] = __uint_as_float(v.w);
-        } else {
-            const uint2 v = nt_load8(p + j);
-            f[0] = T::to_f((uint16_t)(v.x & 0xffff)); f[1] = T::to_f((uint16_t)(v.x >> 16));
-            f[2] = T::to_f((uint16_t)(v.y & 0xffff)); f[3] = T::to_f((uint16_t)(v.y >> 16));
-        }
-        return;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) f[e] = (j + e < n) ? T::load(p, j + e) : 0.0f;
-}
-
-// 4 elements from one 16-B (f32) / 8-B (16-bit) load
-template <typename T>
-__device__ __forceinline__ void unpack4(const uint4& v, float (&f)[4]) {
-    f[0] = __uint_as_float(v.x); f[1] = __uint_as_float(v.y);
-    f[2] = __uint_as_float(v.z); f[3] = __uint_as_float(v.w);
-}
-template <typename T>
-__device__ __forceinline__ void unpack4(const uint2& v, float (&f)[4]) {
-    f[0] = T::to_f((uint16_t)(v.x & 0xffff)); f[1] = T::to_f((uint16_t)(v.x >> 16));
-    f[2] = T::to_f((uint16_t)(v.y & 0xffff)); f[3] = T::to_f((uint16_t)(v.y >> 16));
-}
-
-template <typename T, bool NTS = true>
-__device__ __forceinline__ void store4(typename T::storage* p, int64_t j, int64_t n, bool vec, const float (&f)[4]) {
-    using S = typename T::storage;
-    if (vec && j + 4 <= n) {
-        if constexpr (sizeof(S) == 4) {
-            const uint4 v = make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
-            if constexpr (NTS) nt_store16(v, p + j);
-            else *reinterpret_cast<uint4*>(p + j) = v;
-        } else {
-            uint2 v;
-            v.x = (uint32_t)T::from_f(f[0]) | ((uint32_t)T::from_f(f[1]) << 16);
-            v.y = (uint32_t)T::from_f(f[2]) | ((uint32_t)T::from_f(f[3]) << 16);
-            if constexpr (NTS) nt_store8(v, p + j);
-            else *reinterpret_cast<uint2*>(p + j) = v;
-        }
-        return;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (j + e < n) p[j + e] = T::from_f(f[e]);
-}
-
-// this wave's index in the grid, through readfirstlane so the compiler knows it (and every
-// tile index and bound derived from it) is wave-uniform: scalar loop control and SGPR-based
-// addresses instead of 64-bit VALU arithmetic and exec-mask branches per tile
-__device__ __forceinline__ int64_t grid_wave() {
-    return (int64_t)blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-}
-
-// the 64-lane tree of the tile sum: s[l] += s[l^h], h = 32..1 (== s[l] + s[l+h])
-__device__ __forceinline__ float wave_tree_sum(float s) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s = s + __shfl_xor(s, o, kWave);
-    return s;
-}
-
-// The same tree with its result in lane 0 only (the streaming kernels store lane 0's):
-// s[l] += s[l+h] for h = 32, 16 by swapping halves across lanes (gfx950's permlane swaps),
-// h = 8..1 by DPP row shifts -- no LDS round trip per level, and 8 instructions where the
-// shuffles above take ~36 plus six ds_bpermute waits.  Every lane of the wave must be active
-__device__ __forceinline__ float wave_tree_sum_lane0(float s) {
-    s = s + __uint_as_float(__builtin_amdgcn_permlane32_swap(__float_as_uint(s), __float_as_uint(s), false, false)[1]);
-    s = s + __uint_as_float(__builtin_amdgcn_permlane16_swap(__float_as_uint(s), __float_as_uint(s), false, false)[1]);
-    s = s + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x108, 0xf, 0xf, false));  // row_shl:8
-    s = s + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x104, 0xf, 0xf, false));  // row_shl:4
-    s = s + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x102, 0xf, 0xf, false));  // row_shl:2
-    s = s + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x101, 0xf, 0xf, false));  // row_shl:1
-    return s;
-}
-
-// lane l + 1's value in even lanes l (an even lane and its odd neighbour share a DPP row)
-__device__ __forceinline__ uint32_t odd_neighbour(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, false);  // row_shl:1
-}
-
-// lane-local part of the tile tree for values a[sub][e]
-__device__ __forceinline__ float lane_tree(const float (&a)[4][4]) {
-    float q[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q[k] = (a[k][0] + a[k][1]) + (a[k][2] + a[k][3]);
-    return (q[0] + q[1]) + (q[2] + q[3]);
-}
 
 // ------------------------------------------------------------------------
 // encode: bits + per-tile |x| partials, one wave per tile
@@ -210,109 +95,6 @@ __global__ __launch_bounds__(kBlock) void onebit_encode_kernel(
 // ------------------------------------------------------------------------
 // finalize: scale = F(partials) / n, header, slack (one workgroup per chunk)
 // ------------------------------------------------------------------------
-__device__ __forceinline__ float tile_from(const float* v, int64_t base, int64_t count, int lane) {
-    float a[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t r = base + k * 256 + lane * 4 + e;
-            const float x = v[r < count ? r : count - 1];  // clamped: no load waits behind a branch
-            a[k][e] = r < count ? x : 0.0f;
-        }
-    return wave_tree_sum(lane_tree(a));
-}
-
-// Levels >= 2 of the chunk tree: lvl[0][0, ceil(m1 / 1024)) holds the level-1 group
-// sums (published by a barrier); returns the root to every thread.
-__device__ __forceinline__ float upper_tree(int64_t m1, float (&lvl)[2][2048]) {
-    const int lane = lane_id(), wave = threadIdx.x / kWave, nw = kObFinalizeThreads / kWave;
-    int cur = 0;
-    bool done = m1 <= kObTile;
-    int64_t m = (m1 + kObTile - 1) / kObTile;
-    while (!done) {
-        const int64_t g = (m + kObTile - 1) / kObTile;
-        for (int64_t i = wave; i < g; i += nw) {
-            const float s = tile_from(lvl[cur], i * kObTile, m, lane);
-            if (lane == 0) lvl[cur ^ 1][i] = s;
-        }
-        __syncthreads();
-        done = m <= kObTile;
-        cur ^= 1;
-        m = g;
-    }
-    return lvl[cur][0];
-}
-
-// The fixed 1024-tree over a chunk's m1 tile partials get(r), by one
-// kObFinalizeThreads workgroup: level 1 -> 2 straight from `get` (each wave takes
-// kFinBatch groups at once and issues all their loads before any tree, so the pass
-// costs one memory latency instead of one per group),
-// the higher levels in LDS.  Every thread returns the total (0 when m1 = 0).
-template <typename Get>
-__device__ __forceinline__ float chunk_tree(const Get& get, int64_t m1, float (&lvl)[2][2048]) {
-    // the wave index through readfirstlane: the compiler then knows the group branches below
-    // are wave-uniform (scalar branches, not exec masks)
-    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-    const int nw = kObFinalizeThreads / kWave;
-    if (m1 <= 0) return 0.0f;
-    int64_t m = m1;
-    const int64_t g1 = (m + kObTile - 1) / kObTile;
-    constexpr int kFinBatch = 4;
-    for (int64_t g0 = wave; g0 < g1; g0 += (int64_t)nw * kFinBatch) {
-        float a[kFinBatch][4][4];
-        if ((g0 + (int64_t)(kFinBatch - 1) * nw + 1) * kObTile <= m) {
-            // every group of the batch is full: one base per group, immediate offsets
-#pragma unroll
-            for (int j = 0; j < kFinBatch; ++j) {
-                const int64_t bj = (g0 + (int64_t)j * nw) * kObTile + lane * 4;
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) a[j][k][e] = get(bj + k * 256 + e);
-            }
-        } else {
-        // otherwise per group, a wave-uniform branch: a full group's loads unconditional,
-        // only the chunk's last, ragged group read element by element (guarded).  Guarded
-        // loads for the whole batch are serialised by the compiler under this workgroup's
-        // 128-VGPR budget: the finalize of 32 groups (one ragged batch) took 10.7 us, this
-        // way 4.6; of 64 (one full batch) 5.3
-#pragma unroll
-        for (int j = 0; j < kFinBatch; ++j) {
-            const int64_t g = g0 + (int64_t)j * nw;
-            const int64_t bj = g * kObTile + lane * 4;
-            if ((g + 1) * kObTile <= m) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) a[j][k][e] = get(bj + k * 256 + e);
-            } else if (g * kObTile < m) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int64_t r = bj + k * 256 + e;
-                        a[j][k][e] = r < m ? get(r) : 0.0f;
-                    }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) a[j][k][e] = 0.0f;
-            }
-        }
-        }
-#pragma unroll
-        for (int j = 0; j < kFinBatch; ++j) {
-            const int64_t g = g0 + (int64_t)j * nw;
-            const float s = wave_tree_sum(lane_tree(a[j]));
-            if (lane == 0 && g < g1) lvl[0][g] = s;
-        }
-    }
-    __syncthreads();
-    return upper_tree(m1, lvl);
-}
-
 __global__ __launch_bounds__(kObFinalizeThreads) void onebit_finalize_kernel(
     const float* __restrict__ partials, int64_t tiles_per_chunk, int64_t in_num_elem, int64_t cs, int target,
     uint8_t* __restrict__ out, int64_t chunk_offset, int64_t out_bytes, int num_chunks) {
@@ -857,15 +639,6 @@ __global__ __launch_bounds__(kBlock) void onebit_one_rank_decode_kernel(const ui
 // ------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------
-static int64_t ob_tiles(int64_t cs) { return (cs + kObTile - 1) / kObTile; }
-
-static int ob_blocks(int64_t tiles, int nact, int target_blocks = kTargetBlocks) {
-    int64_t b = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int64_t cap = (target_blocks + nact - 1) / nact;
-    if (b > cap) b = cap;
-    return (int)(b < 1 ? 1 : b);
-}
-
 // stage 0: encode every tile + finalize; 1: encode tiles [t_begin, t_end) only
 // (bits + |x| partials, no header); 2: finalize only (header + slack from the
 // partials every stage-1 range left in the workspace)

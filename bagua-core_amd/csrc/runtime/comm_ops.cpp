@@ -152,7 +152,7 @@ int env_int(const char* name, long dflt);
 int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_tensor_t* t, uint64_t chunk,
                    int sched, int average);
 enum { kOpCentralized = 1, kOpCentralizedUnfused, kOpCentralizedPipelined, kOpOneBitPipelined, kOpRing,
-       kOpRingUnfused, kOpRingPipelined };
+       kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback };
 
 int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int method, bool fused) {
     OpTimer tm;
@@ -703,6 +703,124 @@ int centralized_pipelined_onebit(BaguaSingleCommunicatorC* c, const bagua_tensor
     return finish_both(c, BAGUA_OK);
 }
 
+// The 1-bit op with error feedback: centralized_pipelined_onebit's
+// structure with the `_ef` kernels.  The worker state (carry, one scale per chunk)
+// compensates what this rank encodes for the alltoall, the server state (carry of
+// the own chunk, one scale) what it re-encodes for the allgather; alltoall,
+// allgather, final decode and segment sizes are the plain op's.  Every piece count
+// -- one included, and one rank -- takes this one path:
+//
+//   stream: E0 E1 .. Ek F | R+F | D0 D1 .. Dk        (E, F, R+F: the _ef kernels)
+//   side  :    A0 A1 .. Ak+hdr   G0+hdr G1 .. Gk
+//
+// Each piece's encode reads the worker scales that the step's one finalize (after
+// the last piece, same stream) then overwrites.
+struct EfState {
+    float *wc, *ws, *sc, *ss;
+};
+
+// a state tensor: F32, on the op's device, exactly `n` elements, 16-B aligned
+int ef_tensor(const bagua_tensor_t* s, uint64_t n, int device, float** out) {
+    if (!s || !s->ptr) return BAGUA_ERR_INVALID_ARG;
+    if (s->dtype != BAGUA_DTYPE_F32 || s->device_id != device) return BAGUA_ERR_INVALID_ARG;
+    if (s->num_elem != n || s->num_elem_allocated != n || s->ptr % 16) return BAGUA_ERR_INVALID_ARG;
+    *out = (float*)(uintptr_t)s->ptr;
+    return BAGUA_OK;
+}
+
+int centralized_onebit_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, const EfState& st,
+                          int pieces) {
+    Chunking k;
+    int rc = plan(c, t, BAGUA_COMPRESSION_ONEBIT, &k);
+    if (rc) return rc;
+    const int caller = pieces;
+    pieces &= BAGUA_PIECES_COUNT_MASK;  // 1-bit pieces are tile ranges: no tapered schedule
+    if (pieces < 1) pieces = k.p == 1 ? 1 : auto_pieces(c, k.cs / 8);  // sign bits per chunk
+    if (k.p > 16) pieces = 1;  // the composed middle step reads the whole tensor
+    if (t->ptr % 16)
+        // the caller's value, not the resolved count: ranks whose alignment differs
+        // resolve it from the same input and build the same piece ranges
+        return with_aligned_copy(c, {t}, [&](const std::vector<const bagua_tensor_t*>& u) {
+            return centralized_onebit_ef(c, u[0], average, st, caller);
+        });
+    DeviceGuard guard(c->device_id);
+    if ((rc = check_schedule(c, kOpOneBitErrorFeedback, BAGUA_COMPRESSION_ONEBIT, t, k.cs, pieces, average))) return rc;
+    if (c->ensure_side(2 * (size_t)pieces + 2)) return BAGUA_ERR_HIP;
+    hipStream_t s0 = c->stream, s1 = c->side;
+    hipEvent_t* encoded = c->events.data();
+    hipEvent_t* gathered = encoded + pieces;
+    hipEvent_t exchanged = gathered[pieces], requantised = gathered[pieces + 1];
+    const int dt = t->dtype, cs = (int)k.cs, p = k.p;
+    void* x = (void*)(uintptr_t)t->ptr;
+    OpBuffer send(c), recv(c);
+    TRY(send.allocate(c->device_id, k.S));
+    TRY(recv.allocate(c->device_id, k.S));
+    uint8_t* sb = send.as<uint8_t>();
+    uint8_t* rb = recv.as<uint8_t>();
+    const size_t ws_bytes = bagua_onebit_workspace_bytes(cs, p);
+    uint64_t wsp = 0;
+    if ((rc = stream_workspace(c->device_id, (uint64_t)(uintptr_t)s0, ws_bytes, &wsp)) != BAGUA_OK)
+        return finish(c, rc);
+    void* ws = (void*)(uintptr_t)wsp;
+    HIP2(hipEventRecord(requantised, s0));
+    HIP2(hipStreamWaitEvent(s1, requantised, 0));
+    // 1. compensate + encode piece by piece (bits + partials of every chunk, carry in
+    // place), headers and the new worker scales last
+    for (int q = 0; q < pieces; ++q) {
+        int tb, te;
+        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
+        if (te > tb)
+            TRY2(bagua_onebit_encode_range_ef(dt, x, (int)t->num_elem, cs, p, sb, k.S, ws, ws_bytes, tb, te, st.wc, st.ws,
+                                              s0));
+        if (q == pieces - 1)
+            TRY2(bagua_onebit_finalize_ef(ws, ws_bytes, (int)t->num_elem, cs, p, sb, k.S, st.ws, s0));
+        HIP2(hipEventRecord(encoded[q], s0));
+    }
+    for (int q = 0; q < pieces; ++q) {
+        int tb, te;
+        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
+        size_t lo, hi;
+        onebit_piece_bytes(k, tb, te, false, &lo, &hi);
+        HIP2(hipStreamWaitEvent(s1, encoded[q], 0));
+        TRY2(exchange_piece(c, k, sb, rb, lo, hi, true));
+        if (q == pieces - 1) TRY2(exchange_piece(c, k, sb, rb, 0, 32, true));  // the headers
+    }
+    HIP2(hipEventRecord(exchanged, s1));
+    // 2. decode the p received segments of the own chunk, reduce, compensate with the
+    // server state, re-encode (the reduced chunk is not stored)
+    HIP2(hipStreamWaitEvent(s0, exchanged, 0));
+    rc = bagua_onebit_reduce_requantize_ef(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, ws, ws_bytes, st.sc, st.ss, s0);
+    if (rc == BAGUA_ERR_UNSUPPORTED) {
+        // more chunks than the fused kernel takes: the reference's decode + reduce into the
+        // tensor, then the worker encode on the own chunk alone (one chunk, into its segment)
+        const bagua_tensor_t rv = u8_view(recv.ptr(), k.S, c->device_id);
+        const size_t co = k.S / k.p;
+        TRY2(bagua_tensor_decompress_from(t, BAGUA_COMPRESSION_ONEBIT, p, &rv, (uint64_t)(uintptr_t)s0));
+        TRY2(bagua_tensor_reduce_inplace(t, p, k.rank, average, (uint64_t)(uintptr_t)s0));
+        rc = bagua_onebit_compress_ef(dt, (const uint8_t*)x + (size_t)k.rank * k.cs * bagua_dtype_bytes(dt), cs, cs, 1,
+                                      sb + (size_t)k.rank * co, co, ws, ws_bytes, -1, st.sc, st.ss, s0);
+    }
+    TRY2(rc);
+    HIP2(hipEventRecord(requantised, s0));
+    // 3. allgather (headers with piece 0) + decode piece by piece
+    HIP2(hipStreamWaitEvent(s1, requantised, 0));
+    for (int q = 0; q < pieces; ++q) {
+        int tb, te;
+        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
+        size_t lo, hi;
+        onebit_piece_bytes(k, tb, te, q == 0, &lo, &hi);
+        TRY2(exchange_piece(c, k, sb, rb, lo, hi, false));
+        HIP2(hipEventRecord(gathered[q], s1));
+    }
+    for (int q = 0; q < pieces; ++q) {
+        int tb, te;
+        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
+        HIP2(hipStreamWaitEvent(s0, gathered[q], 0));
+        if (te > tb) TRY2(bagua_onebit_decompress_range(dt, sb, k.S, cs, p, x, tb, te, s0));
+    }
+    return finish_both(c, BAGUA_OK);
+}
+
 // ---- ring exchange schedule ------------------------------------------------
 // The reference sends the whole compressed bucket straight to both ring peers
 // (decentralized_low_precision_synchronous.rs:98-115).  On a fully connected
@@ -882,6 +1000,29 @@ int bagua_centralized_low_precision_pipelined(BaguaSingleCommunicatorC* c, const
     if (method == BAGUA_COMPRESSION_ONEBIT) return centralized_pipelined_onebit(c, t, average, pieces);
     if (method != BAGUA_COMPRESSION_MINMAX_UINT8) return centralized(c, t, average, method, true);
     return centralized_pipelined(c, t, average, pieces);
+}
+
+int bagua_centralized_onebit_error_feedback(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
+                                            const bagua_tensor_t* worker_carry, const bagua_tensor_t* worker_scales,
+                                            const bagua_tensor_t* server_carry, const bagua_tensor_t* server_scale,
+                                            int pieces) {
+    // every refusal before anything is launched or posted
+    if (!c || !c->t || !t || !t->ptr) return BAGUA_ERR_INVALID_ARG;
+    if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
+    if (!is_float_dtype(t->dtype)) return BAGUA_ERR_UNSUPPORTED;
+    if (t->num_elem != t->num_elem_allocated) return BAGUA_ERR_UNSUPPORTED;  // partly valid tensors: the plain op only
+    const uint64_t p = c->nranks;
+    if (!t->num_elem || t->num_elem % p || t->num_elem > 0x7fffffffULL || t->device_id != (int)c->device_id)
+        return BAGUA_ERR_INVALID_ARG;
+    const uint64_t cs = t->num_elem / p;
+    EfState st{};
+    int rc;
+    if ((rc = ef_tensor(worker_carry, t->num_elem, t->device_id, &st.wc)) ||
+        (rc = ef_tensor(worker_scales, p, t->device_id, &st.ws)) ||
+        (rc = ef_tensor(server_carry, cs, t->device_id, &st.sc)) ||
+        (rc = ef_tensor(server_scale, 1, t->device_id, &st.ss)))
+        return rc;
+    return centralized_onebit_ef(c, t, average, st, pieces);
 }
 
 int bagua_centralized_low_precision_synchronous(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,

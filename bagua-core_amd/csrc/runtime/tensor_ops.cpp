@@ -196,6 +196,45 @@ int bagua_tensor_compress_into(const bagua_tensor_t* t, int method, int n_chunks
     return compress_into(t, method, n_chunks, stream, target_chunk, out->ptr, bytes);
 }
 
+// the 1-bit compress with error-feedback state (bagua_onebit_compress_ef): `carry`
+// (num_elem F32) and `scales` (n_chunks F32) on the tensor's device, 16-B aligned
+int bagua_tensor_compress_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
+                                         const bagua_tensor_t* carry, const bagua_tensor_t* scales,
+                                         bagua_tensor_t* out) {
+    size_t cs = 0;
+    int rc = check_chunks(t, n_chunks, &cs);
+    if (rc) return rc;
+    if (!out || !carry || !scales) return BAGUA_ERR_INVALID_ARG;
+    if (!codec_dtype(t->dtype)) return BAGUA_ERR_INVALID_ARG;
+    if (t->num_elem != t->num_elem_allocated) return BAGUA_ERR_UNSUPPORTED;  // every chunk fully valid
+    for (const bagua_tensor_t* s : {carry, scales}) {
+        const uint64_t want = s == carry ? t->num_elem : (uint64_t)n_chunks;
+        if (s->dtype != BAGUA_DTYPE_F32 || s->device_id != t->device_id || s->num_elem != want ||
+            s->num_elem_allocated != want || !s->ptr || s->ptr % 16)
+            return BAGUA_ERR_INVALID_ARG;
+    }
+    const size_t bytes = bagua_onebit_compressed_bytes((int)cs, n_chunks);
+    const size_t ws_bytes = bagua_onebit_workspace_bytes((int)cs, n_chunks);
+    uint64_t ws = 0;
+    if ((rc = stream_workspace(t->device_id, stream, ws_bytes, &ws)) != BAGUA_OK) return rc;
+    uint64_t p = 0;
+    if ((rc = pool_alloc(t->device_id, bytes, &p)) != BAGUA_OK) return rc;
+    rc = bagua_onebit_compress_ef(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)cs, n_chunks,
+                                  (uint8_t*)(uintptr_t)p, bytes, (void*)(uintptr_t)ws, ws_bytes, -1,
+                                  (float*)(uintptr_t)carry->ptr, (float*)(uintptr_t)scales->ptr,
+                                  (void*)(uintptr_t)stream);
+    if (rc) {
+        pool_free(p);
+        return rc;
+    }
+    out->ptr = p;
+    out->num_elem = bytes;
+    out->num_elem_allocated = bytes;
+    out->dtype = BAGUA_DTYPE_U8;
+    out->device_id = t->device_id;
+    return BAGUA_OK;
+}
+
 int bagua_tensor_decompress_from(const bagua_tensor_t* t, int method, int n_chunks, const bagua_tensor_t* compressed,
                                  uint64_t stream) {
     size_t cs = 0;

@@ -90,6 +90,12 @@ int bagua_tensor_compress(const bagua_tensor_t* t, int method, int n_chunks, uin
 /* the same into a caller-provided U8 buffer of exactly bagua_compressed_size() bytes */
 int bagua_tensor_compress_into(const bagua_tensor_t* t, int method, int n_chunks, uint64_t stream,
                                int target_chunk, const bagua_tensor_t* out);
+/* bagua_tensor_compress with the "OneBitSignScale" codec and error-feedback state
+ * (bagua_onebit_compress_ef): `carry` (t->num_elem F32) and `scales` (n_chunks F32) on the
+ * tensor's device, 16-B aligned, updated in place on `stream`; every chunk compressed. */
+int bagua_tensor_compress_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
+                                         const bagua_tensor_t* carry, const bagua_tensor_t* scales,
+                                         bagua_tensor_t* out);
 /* RawBaguaTensor::decompress_from (datatypes/mod.rs:398-446) */
 int bagua_tensor_decompress_from(const bagua_tensor_t* t, int method, int n_chunks,
                                  const bagua_tensor_t* compressed, uint64_t stream);
@@ -174,6 +180,22 @@ int bagua_centralized_low_precision_synchronous(BaguaSingleCommunicatorC* comm, 
  * kernels cannot take run unpieced. */
 int bagua_centralized_low_precision_pipelined(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t, int average,
                                               int method, int pieces);
+/* The 1-bit op with error feedback: the pipelined op above with the
+ * "OneBitSignScale" codec, where each rank carries its quantisation error into the next
+ * step -- once for what it encodes for the alltoall (worker state) and once for the own
+ * chunk it re-encodes for the allgather (server state).  The state is the caller's, F32 on
+ * the tensor's device, 16-B aligned, zero before the first step, and holds n = t->num_elem,
+ * nranks, n / nranks and 1 elements (worker_carry, worker_scales, server_carry,
+ * server_scale).  Wire format, collectives and segment sizes are the plain op's; with zero
+ * state the result equals it.  `pieces` as above (0 automatic, 1 unpieced); every count
+ * gives the same bits.  Its own kind under BAGUA_CHECK_SCHEDULE: a rank running the plain
+ * op against it is a schedule mismatch.  Refused before anything is launched:
+ * num_elem < num_elem_allocated (BAGUA_ERR_UNSUPPORTED), state of the wrong size, dtype,
+ * device or alignment (BAGUA_ERR_INVALID_ARG); there is no hierarchical form. */
+int bagua_centralized_onebit_error_feedback(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t, int average,
+                                            const bagua_tensor_t* worker_carry, const bagua_tensor_t* worker_scales,
+                                            const bagua_tensor_t* server_carry, const bagua_tensor_t* server_scale,
+                                            int pieces);
 /* the reference's unfused sequence, kept for A/B measurement and parity */
 int bagua_centralized_low_precision_synchronous_unfused(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t,
                                                         int average, int method);
@@ -251,7 +273,8 @@ enum {
     BAGUA_BUCKET_OP_CENTRALIZED_LOW_PRECISION = 1,   /* centralized_low_precision_synchronous.rs */
     BAGUA_BUCKET_OP_CENTRALIZED_FULL_PRECISION = 2,  /* centralized_full_precision_synchronous.rs */
     BAGUA_BUCKET_OP_DECENTRALIZED_LOW_PRECISION = 3, /* decentralized_low_precision_synchronous.rs */
-    BAGUA_BUCKET_OP_CALLBACK = 4                     /* python_ffi_op.rs: callback(user, bucket name) */
+    BAGUA_BUCKET_OP_CALLBACK = 4,                    /* python_ffi_op.rs: callback(user, bucket name) */
+    BAGUA_BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK = 5 /* bagua_centralized_onebit_error_feedback */
 };
 
 typedef struct bagua_bucket_op {
@@ -266,6 +289,10 @@ typedef struct bagua_bucket_op {
     /* hierarchical mode when set: the node's communicator (comm = the internode one,
      * NULL on the node's workers), see bagua_*_hierarchical */
     BaguaSingleCommunicatorC* intranode;
+    /* BAGUA_BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK: the op's state (F32, on the bucket's
+     * device, sized for the flattened bucket; see bagua_centralized_onebit_error_feedback).
+     * Zeroed = absent, so initialisers written before these fields existed mean what they meant. */
+    bagua_tensor_t ef_worker_carry, ef_worker_scales, ef_server_carry, ef_server_scale;
 } bagua_bucket_op_t;
 
 /* NULL on error (*status says why): empty list, mixed dtype / device, allocated < num_elem */

@@ -156,6 +156,44 @@ int bagua_onebit_reduce_requantize(int dtype, const uint8_t* input, size_t input
                                    int num_chunks, void* tensor, int average, uint8_t* output, size_t output_bytes,
                                    int target_chunk, void* workspace, size_t workspace_bytes, bagua_stream_t stream);
 
+/* 1-bit codec with error feedback: the same wire format, plus
+ * caller-owned f32 state, 16-B aligned and zero before the first step, that carries
+ * each step's quantisation error into the next.  Worker state: carry[chunk_size *
+ * num_chunks] and scales[num_chunks]; server state (the middle step): carry[chunk_size]
+ * and scale[1].  The carry holds the previous step's compensated value v; per element,
+ * with s the chunk's previous scale,  v = x + (carry - as_stored_T(carry < 0 ? -s : s)),
+ * carry = v in place, and the segment is the plain encode of v as an f32 array (with zero
+ * state: of x).  Every chunk must be fully valid (input_num_element == chunk_size *
+ * num_chunks); a null or misaligned state pointer, another element count and any dtype
+ * but F32 / F16 / BF16 are BAGUA_ERR_INVALID_ARG.  Calls of one state must be ordered on
+ * one stream: an encode reads the scales the previous step's finalize stored. */
+int bagua_onebit_ef_state_bytes(int chunk_size, int num_chunks, size_t* carry_bytes, size_t* scale_bytes);
+/* bagua_onebit_compress's arguments plus the state; target_chunk = -1 only.
+ * Workspace: bagua_onebit_workspace_bytes. */
+int bagua_onebit_compress_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                             uint8_t* output, size_t output_bytes, void* workspace, size_t workspace_bytes,
+                             int target_chunk, float* carry, float* scales, bagua_stream_t stream);
+/* The pieced form (see bagua_onebit_encode_range): tiles [tile_begin, tile_end) of every
+ * chunk are compensated and encoded (carry updated, scales read); once every range is
+ * encoded, bagua_onebit_finalize_ef writes the headers and slack as bagua_onebit_finalize
+ * does and stores each chunk's new scale into `scales`. */
+int bagua_onebit_encode_range_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                                 uint8_t* output, size_t output_bytes, void* workspace, size_t workspace_bytes,
+                                 int tile_begin, int tile_end, float* carry, const float* scales,
+                                 bagua_stream_t stream);
+int bagua_onebit_finalize_ef(const void* workspace, size_t workspace_bytes, int input_num_element, int chunk_size,
+                             int num_chunks, uint8_t* output, size_t output_bytes, float* scales,
+                             bagua_stream_t stream);
+/* bagua_onebit_reduce_requantize with the server state: the reduced value of element j of
+ * chunk `target_chunk`, as stored in T, is the x of the rule above (carry[j], scale[0]);
+ * the reduced chunk is never stored.  BAGUA_ERR_UNSUPPORTED for num_chunks > 16: callers
+ * then run bagua_onebit_decompress + bagua_reduce_chunks and bagua_onebit_compress_ef on
+ * the own chunk (one chunk, into its segment). */
+int bagua_onebit_reduce_requantize_ef(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                      int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                      int target_chunk, void* workspace, size_t workspace_bytes, float* carry,
+                                      float* scale, bagua_stream_t stream);
+
 /* ======================================================================== */
 /* v2 — chunk reduction and elementwise ops                                  */
 /* ======================================================================== */
