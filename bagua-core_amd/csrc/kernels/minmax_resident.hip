@@ -21,6 +21,11 @@
 //           read last are the ones the 256 MiB Infinity Cache still holds),
 //           then the LDS part, then the VGPR part, and write header / slack.
 //
+// minmax_resident_encode_kernel_stack (the f32 and f16 default) runs the passes in
+// stack order instead -- pass 1: streamed, parked, held; pass 2: held, parked,
+// streamed -- so the held vectors reuse the streaming buffers' registers and more
+// of the chunk stays on chip without scratch (see the comment above that kernel).
+//
 // Per-launch state lives in a library-owned slot (one per stream; the
 // hipStreamPerThread sentinel gets one per host thread) that is never reset:
 // launch k on a slot draws tickets [kG, (k+1)G) from monotonic counters, so
@@ -235,7 +240,9 @@ __device__ __forceinline__ bool sweep_chunk(const ResidentArgs& a, int cl, uint3
 // the slice otherwise.  Threads may disagree about a granule that lands
 // meanwhile; every slice is then still covered whole (by the granule some
 // thread took, or by all threads' strided re-reads), so the union is exact.
-template <typename T, int BLOCK>
+// LEAN: the re-read loop is not unrolled (a caller with no registers to spare on this
+// rare path)
+template <typename T, int BLOCK, bool LEAN = false>
 __device__ void fold_missing_slices(const ResidentArgs& a, int cl, uint32_t tag, uint32_t& lo, uint32_t& hi) {
     const int t = (int)threadIdx.x;
     for (int b = 0; b < a.bpc; ++b) {
@@ -250,7 +257,12 @@ __device__ void fold_missing_slices(const ResidentArgs& a, int cl, uint32_t tag,
         }
         const SliceGeom<T, BLOCK> sg(a, gg);
         const uint4* __restrict__ v = reinterpret_cast<const uint4*>(sg.src + sg.j0);
-        for (int64_t i = sg.v0 + t; i < sg.v1; i += BLOCK) fold_vec<T>(v[i], lo, hi);
+        if constexpr (LEAN) {
+#pragma unroll 1
+            for (int64_t i = sg.v0 + t; i < sg.v1; i += BLOCK) fold_vec<T>(v[i], lo, hi);
+        } else {
+            for (int64_t i = sg.v0 + t; i < sg.v1; i += BLOCK) fold_vec<T>(v[i], lo, hi);
+        }
         if (sg.last) fold_scalars<T, BLOCK>(a, sg, lo, hi);
     }
 }
@@ -490,6 +502,289 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
         __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// One tile of SB rows whose vector indices are clamped to `vl` (the slice's last
+// vector): a ragged tile loads like a full one, all SB loads in flight together;
+// the duplicates never change a min/max, and pass 2 stores only what is in range.
+template <int SB, int BLOCK, bool NT>
+__device__ __forceinline__ void load_tile_clamped(const uint4* __restrict__ v, int64_t base, int64_t vl, int t,
+                                                  uint4 (&r)[SB]) {
+#pragma unroll
+    for (int j = 0; j < SB; ++j) {
+        const int64_t i = base + j * BLOCK + t;
+        r[j] = NT ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
+    }
+}
+
+// Stack order: the same slice layout as minmax_resident_encode_kernel (rows [0, R)
+// of a slice held in VGPRs, rows [R, R + H) parked in LDS, the rest streamed; a row
+// is BLOCK vectors), with the passes turned round so that the held rows are never
+// live together with the streaming buffers:
+//
+//   pass 1: the streamed rows first (ascending, double-buffered), then the parked
+//           rows, then the held rows, loaded last into the registers the streaming
+//           buffers no longer need
+//   pass 2: the held rows first, then the parked rows, then the streamed rows from
+//           the top down.  The two top streamed tiles are requested once the held
+//           rows are stored (their registers are free by then), so their latency
+//           runs under the parked rows' quantisation.
+//
+// The register budget is max(4R, streaming buffers) + temporaries instead of their
+// sum, which is what lets R grow past 28 at BLOCK = 512 without scratch.  Slice
+// ownership, scalars, header and slack, the exchange, the give-up path, tickets
+// and the drain counter are those of minmax_resident_encode_kernel.
+// EARLY: the first streamed tile is requested before the ticket is drawn (the tag
+// is only needed when the partials are published).
+// Trace stamps: 0 start, 1 pass 1 end, 2 exchange end, 6 held rows stored,
+// 7 parked rows stored, 3 end.
+template <typename T, int BLOCK, int R, int H, int SB, int NTM, bool EARLY, bool ASC>
+__global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(ResidentArgs a) {
+    constexpr int N = Vec<T>::N;
+    constexpr bool NT = (NTM & 1) != 0;
+    constexpr bool NT1 = (NTM & 2) != 0;
+    constexpr int W = BLOCK / kWave;
+    static_assert(R > 0 && H > 0, "the stack order keeps rows in VGPRs and in LDS");
+    extern __shared__ __attribute__((aligned(16))) uint4 smem[];
+    uint4* park = smem;
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // 2*W + 4 words
+    const int t = (int)threadIdx.x;
+    const int g = (int)blockIdx.x;
+    const int lane_c = g % kResLanes;
+    const bool idle = g >= a.nact * a.bpc;  // the grid is the CU count on every launch of the slot
+
+    const SliceGeom<T, BLOCK> s(a, idle ? 0 : g);
+    const uint4* __restrict__ v = reinterpret_cast<const uint4*>(s.src + s.j0);
+    const int64_t v0 = s.v0, v1 = s.v1;
+    const int64_t vl = v1 - 1;                              // clamp target (used only when v1 > v0)
+    const int64_t stream0 = v0 + (int64_t)(R + H) * BLOCK;  // first streamed vector
+    const int64_t tile = (int64_t)SB * BLOCK;
+    const int64_t nfull = v1 > stream0 ? (v1 - stream0) / tile : 0;
+    const int64_t top = stream0 + nfull * tile;  // the ragged top tile [top, v1), possibly empty
+
+    uint4 ra[SB];
+    if (EARLY && !idle && nfull > 0) load_tile<SB, BLOCK>(v, stream0, t, ra);
+    if (t == 0) {
+        const uint64_t ticket = __hip_atomic_fetch_add(&a.slot->ticket[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_AGENT);
+        scratch[2 * W] = tag_of_ticket(ticket, a.grid, lane_c);
+    }
+    __syncthreads();
+    const uint32_t tag = scratch[2 * W];
+    trace_stamp(a, g, 0);
+    if (idle) {
+        if (t == 0)
+            __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+
+    // ---- pass 1 ------------------------------------------------------------
+    uint32_t lo = min_space(T::init_max());
+    uint32_t hi = max_space(-T::init_max());
+    uint4 held[R];
+    if (v1 > v0) {
+        uint4 rb[SB];
+        if (nfull > 0) {
+            if (!EARLY) load_tile<SB, BLOCK>(v, stream0, t, ra);
+            for (int64_t i = 0; i < nfull; i += 2) {
+                // unconditional (clamped) prefetches keep the wait counts static
+                load_tile<SB, BLOCK>(v, stream0 + (i + 1 < nfull ? i + 1 : nfull - 1) * tile, t, rb);
+#pragma unroll
+                for (int j = 0; j < SB; ++j) fold_vec<T>(ra[j], lo, hi);
+                load_tile<SB, BLOCK>(v, stream0 + (i + 2 < nfull ? i + 2 : nfull - 1) * tile, t, ra);
+                if (i + 1 < nfull) {
+#pragma unroll
+                    for (int j = 0; j < SB; ++j) fold_vec<T>(rb[j], lo, hi);
+                }
+            }
+        }
+        // the ragged top tile and the first batch of parked rows are requested together
+        uint4 cur[SB], nxt[SB];
+        if (v1 > top) load_tile_clamped<SB, BLOCK, false>(v, top, vl, t, rb);
+#pragma unroll
+        for (int j = 0; j < SB; ++j) {
+            if (j < H) {
+                const int64_t i = v0 + (int64_t)(R + j) * BLOCK + t;
+                cur[j] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
+            }
+        }
+        if (v1 > top) {
+#pragma unroll
+            for (int j = 0; j < SB; ++j) fold_vec<T>(rb[j], lo, hi);
+        }
+#pragma unroll
+        for (int kb = 0; kb < H; kb += SB) {
+#pragma unroll
+            for (int j = 0; j < SB; ++j) {
+                if (kb + SB + j < H) {
+                    const int64_t i = v0 + (int64_t)(R + kb + SB + j) * BLOCK + t;
+                    nxt[j] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < SB; ++j) {
+                if (kb + j < H) {
+                    fold_vec<T>(cur[j], lo, hi);
+                    park[(kb + j) * BLOCK + t] = cur[j];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < SB; ++j) cur[j] = nxt[j];
+        }
+        // the held rows, last: every streaming buffer above is dead.  The scheduling
+        // barriers keep it so: without them the scheduler lifts these loads over the
+        // parked rows and expands every row's keys at once, which spills.
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const int64_t i = v0 + (int64_t)k * BLOCK + t;
+            held[k] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            fold_vec<T>(held[k], lo, hi);
+            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if (s.last) fold_scalars<T, BLOCK>(a, s, lo, hi);
+    lo = wave_umin(lo);
+    hi = wave_umin(hi);
+    const int w = t / kWave;
+    if (lane_id() == 0) { scratch[w] = lo; scratch[W + w] = hi; }
+    __syncthreads();
+    if (t == 0) {
+#pragma unroll
+        for (int i = 1; i < W; ++i) { lo = min(lo, scratch[i]); hi = min(hi, scratch[W + i]); }
+        uint64_t* mine = a.slot->gran + 2 * (int64_t)g;
+        __hip_atomic_store(mine, ((uint64_t)tag << 32) | lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mine + 1, ((uint64_t)tag << 32) | hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    trace_stamp(a, g, 1);
+
+    // ---- exchange ------------------------------------------------------------
+    if (w == 0) {
+        const uint64_t deadline = wall_clock64() + a.timeout_ticks;
+        uint32_t l = 0, h = 0;
+        const bool ok = sweep_chunk(a, s.cl, tag, deadline, l, h, true);
+        if (lane_id() == 0) {
+            scratch[2 * W + 1] = ok ? 1u : 0u;
+            scratch[2 * W + 2] = l;
+            scratch[2 * W + 3] = h;
+        }
+    }
+    __syncthreads();
+    if (scratch[2 * W + 1] == 0u) {
+        // gave up waiting: the whole workgroup folds the missing slices itself
+        if (t == 0) __hip_atomic_fetch_add(&a.slot->gave_up, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t l = 0xffffffffu, h = 0xffffffffu;
+        fold_missing_slices<T, BLOCK, true>(a, s.cl, tag, l, h);
+        l = wave_umin(l);
+        h = wave_umin(h);
+        if (lane_id() == 0) { scratch[w] = l; scratch[W + w] = h; }
+        __syncthreads();
+        if (t == 0) {
+#pragma unroll
+            for (int i = 1; i < W; ++i) { l = min(l, scratch[i]); h = min(h, scratch[W + i]); }
+            scratch[2 * W + 2] = l;
+            scratch[2 * W + 3] = h;
+        }
+        __syncthreads();
+    }
+    const float mn = from_min_space(scratch[2 * W + 2]), mx = from_max_space(scratch[2 * W + 3]);
+    const QParams q = make_qparams(mn, mx);
+    trace_stamp(a, g, 2);
+
+    // ---- pass 2 ------------------------------------------------------------
+    write_extras<T, BLOCK>(a, s, mn, mx, q);
+    uint8_t* vdst = s.payload + s.j0;
+    const bool whole = stream0 <= v1;  // the whole on-chip part is inside the slice: no per-vector guards
+    uint8_t* vd = vdst + (v0 + t) * N;
+    // a short slice's guard: its vector count against the lane's offset, in 32 bits
+    const int nloc = (int)(v1 - v0 < (int64_t)(R + H) * BLOCK ? (v1 > v0 ? v1 - v0 : 0) : (int64_t)(R + H) * BLOCK);
+    if (whole) {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            quant_store<T>(held[k], q, vd + (int64_t)k * BLOCK * N);
+            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // four rows' temporaries at a time
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+            if (k * BLOCK + t < nloc) quant_store<T>(held[k], q, vd + (int64_t)k * BLOCK * N);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // no streamed tile is requested while held rows are live
+    trace_stamp(a, g, 6);
+    // the two top streamed tiles (the ragged one, then the top full one), in flight
+    // while the parked rows are quantised
+    // (buffers of their own: pass 1's would count as live across the exchange)
+    uint4 qa[SB], qb[SB];
+    if (v1 > top) load_tile_clamped<SB, BLOCK, NT>(v, top, vl, t, qb);
+    if (nfull > 0) load_tile<SB, BLOCK, NT>(v, stream0 + (ASC ? 0 : nfull - 1) * tile, t, qa);
+    if (whole) {
+#pragma unroll
+        for (int kb = 0; kb < H; kb += SB) {
+            uint4 r[SB];
+#pragma unroll
+            for (int j = 0; j < SB; ++j)
+                if (kb + j < H) r[j] = park[(kb + j) * BLOCK + t];
+#pragma unroll
+            for (int j = 0; j < SB; ++j)
+                if (kb + j < H) quant_store<T>(r[j], q, vd + (int64_t)(R + kb + j) * BLOCK * N);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < H; ++k)
+            if ((R + k) * BLOCK + t < nloc)
+                quant_store<T>(park[k * BLOCK + t], q, vd + (int64_t)(R + k) * BLOCK * N);
+    }
+    trace_stamp(a, g, 7);
+    if (v1 > top) {
+#pragma unroll
+        for (int j = 0; j < SB; ++j) {
+            const int64_t i = top + j * BLOCK + t;
+            if (i < v1) quant_store<T>(qb[j], q, vdst + i * N);
+        }
+    }
+    if (ASC && nfull > 0) {
+        // full tiles double-buffered in pass 1's order: the tiles that have waited longest
+        // in the Infinity Cache are re-read before the payload stores push them out
+        for (int64_t i = 0; i < nfull; i += 2) {
+            load_tile<SB, BLOCK, NT>(v, stream0 + (i + 1 < nfull ? i + 1 : nfull - 1) * tile, t, qb);
+            const int64_t ba = stream0 + i * tile;
+#pragma unroll
+            for (int j = 0; j < SB; ++j) quant_store<T>(qa[j], q, vdst + (ba + j * BLOCK + t) * N);
+            load_tile<SB, BLOCK, NT>(v, stream0 + (i + 2 < nfull ? i + 2 : nfull - 1) * tile, t, qa);
+            if (i + 1 < nfull) {
+                const int64_t bb = ba + tile;
+#pragma unroll
+                for (int j = 0; j < SB; ++j) quant_store<T>(qb[j], q, vdst + (bb + j * BLOCK + t) * N);
+            }
+        }
+    } else if (nfull > 0) {
+        // full tiles double-buffered from the top down (what pass 1 read last of the
+        // streamed part is re-read first)
+        for (int64_t i = nfull - 1; i >= 0; i -= 2) {
+            load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 1 ? i - 1 : 0) * tile, t, qb);
+            const int64_t ba = stream0 + i * tile;
+#pragma unroll
+            for (int j = 0; j < SB; ++j) quant_store<T>(qa[j], q, vdst + (ba + j * BLOCK + t) * N);
+            load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 2 ? i - 2 : 0) * tile, t, qa);
+            if (i >= 1) {
+                const int64_t bb = ba - tile;
+#pragma unroll
+                for (int j = 0; j < SB; ++j) quant_store<T>(qb[j], q, vdst + (bb + j * BLOCK + t) * N);
+            }
+        }
+    }
+    if (a.trace != nullptr) {
+        __syncthreads();
+        trace_stamp(a, g, 3);
+    }
+    // counted last, as in minmax_resident_encode_kernel
+    if (t == 0)
+        __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------
@@ -544,7 +839,9 @@ static ResidentDevice g_res_dev[64];
 // kernel configurations: {BLOCK, R vectors per lane in VGPRs, H per lane in LDS, SB stream batch}
 struct ResidentCfg {
     int block, r, h, sb;
-    int ntm;  // non-temporal loads: bit 0 pass-2 re-reads, bit 1 pass-1 loads of the on-chip part
+    int ntm;    // non-temporal loads: bit 0 pass-2 re-reads, bit 1 pass-1 loads of the on-chip part
+    int stack;  // bit 0: minmax_resident_encode_kernel_stack (stack-order passes); bit 1: its first tile
+                // requested before the ticket; bit 2: pass 2 re-reads the streamed tiles bottom-up
 };
 static constexpr ResidentCfg kResCfg[] = {
     {256, 32, 39, 8, 0},   // 0
@@ -561,6 +858,24 @@ static constexpr ResidentCfg kResCfg[] = {
     {512, 28, 19, 8, 1},       // 11
     {512, 28, 19, 8, 3},       // 12: 11 + the on-chip part loaded non-temporally
     {512, 28, 19, 8, 2},       // 13: only the on-chip part non-temporal
+    // stack-order passes (minmax_resident_encode_kernel_stack): held rows and streaming
+    // buffers share registers, so R grows without scratch; non-temporal as in 12
+    {512, 40, 19, 8, 3, 1},  // 14
+    {512, 44, 19, 8, 3, 1},  // 15
+    {512, 48, 19, 8, 3, 1},  // 16
+    {512, 52, 19, 4, 3, 1},  // 17 (R = 52 with SB = 8 needs scratch: not built)
+    {512, 48, 19, 4, 3, 1},  // 18
+    {512, 52, 19, 4, 3, 3},  // 19: 17 with the first streamed tile requested before the ticket
+    {512, 28, 19, 8, 3, 1},  // 20: the order alone, at 12's R
+    {512, 48, 19, 8, 3, 3},  // 21: 16 with the first streamed tile requested before the ticket
+    {512, 44, 19, 8, 3, 3},  // 22: 15, likewise
+    {512, 52, 19, 4, 3, 5},  // 23: 17 with pass 2's re-read bottom-up
+    {512, 52, 19, 4, 3, 7},  // 24: 19, likewise
+    {512, 52, 19, 4, 1, 1},  // 25: 17 with the on-chip part loaded with the default policy
+    {512, 52, 19, 4, 1, 5},  // 26: 23, likewise
+    {512, 48, 19, 4, 3, 5},  // 27: 18 bottom-up
+    {512, 44, 19, 4, 3, 5},  // 28
+    {512, 44, 19, 4, 3, 1},  // 29
 };
 constexpr int kResNumCfg = (int)(sizeof(kResCfg) / sizeof(kResCfg[0]));
 // 12: config 11 with the on-chip part of pass 1 also loaded non-temporally.  The
@@ -570,6 +885,23 @@ constexpr int kResNumCfg = (int)(sizeof(kResCfg) / sizeof(kResCfg[0]));
 // on-chip part non-temporal with default re-reads, shortens the encode to 78-80 us
 // but slows the decode after it by as much)
 constexpr int kResDefaultCfg = 12;
+// Per dtype, from the stack-order sweep (profiles/resident_stack_ab.jsonl):
+// f32 takes 24 (R = 52, 55 % of the bucket on chip, 256 VGPRs, no scratch) and f16 takes 29
+// (R = 44: the 16-bit kernels need more temporaries); bf16 stays on 12, its best stack
+// row (18) gaining less than the run-to-run spread.  No default may use scratch
+// (bagua_minmax_u8_resident_cfg_info, test_default_rows_use_no_scratch).
+template <typename T>
+constexpr int resident_default_cfg() {
+    return kResDefaultCfg;
+}
+template <>
+constexpr int resident_default_cfg<F32>() {
+    return 24;
+}
+template <>
+constexpr int resident_default_cfg<F16>() {
+    return 29;
+}
 
 static size_t resident_lds_bytes(const ResidentCfg& c) {
     return (size_t)c.h * c.block * 16 + 16 * ((2 * (c.block / kWave) + 4 + 3) / 4);
@@ -578,7 +910,11 @@ static size_t resident_lds_bytes(const ResidentCfg& c) {
 template <typename T, int CFG>
 static void* resident_kernel_ptr() {
     constexpr ResidentCfg c = kResCfg[CFG];
-    return reinterpret_cast<void*>(&minmax_resident_encode_kernel<T, c.block, c.r, c.h, c.sb, c.ntm>);
+    if constexpr (c.stack != 0)
+        return reinterpret_cast<void*>(
+            &minmax_resident_encode_kernel_stack<T, c.block, c.r, c.h, c.sb, c.ntm, (c.stack & 2) != 0, (c.stack & 4) != 0>);
+    else
+        return reinterpret_cast<void*>(&minmax_resident_encode_kernel<T, c.block, c.r, c.h, c.sb, c.ntm>);
 }
 
 template <typename T>
@@ -598,6 +934,22 @@ static void* resident_kernel_for(int cfg) {
         case 11: return resident_kernel_ptr<T, 11>();
         case 12: return resident_kernel_ptr<T, 12>();
         case 13: return resident_kernel_ptr<T, 13>();
+        case 14: return resident_kernel_ptr<T, 14>();
+        case 15: return resident_kernel_ptr<T, 15>();
+        case 16: return resident_kernel_ptr<T, 16>();
+        case 17: return resident_kernel_ptr<T, 17>();
+        case 18: return resident_kernel_ptr<T, 18>();
+        case 19: return resident_kernel_ptr<T, 19>();
+        case 20: return resident_kernel_ptr<T, 20>();
+        case 21: return resident_kernel_ptr<T, 21>();
+        case 22: return resident_kernel_ptr<T, 22>();
+        case 23: return resident_kernel_ptr<T, 23>();
+        case 24: return resident_kernel_ptr<T, 24>();
+        case 25: return resident_kernel_ptr<T, 25>();
+        case 26: return resident_kernel_ptr<T, 26>();
+        case 27: return resident_kernel_ptr<T, 27>();
+        case 28: return resident_kernel_ptr<T, 28>();
+        case 29: return resident_kernel_ptr<T, 29>();
     }
     return nullptr;
 }
@@ -719,7 +1071,7 @@ static ResidentPlan resident_plan(const void* input, int64_t in_num_elem, int64_
                                   int64_t out_bytes, int target, hipStream_t s) {
     using S = typename T::storage;
     ResidentPlan pl;
-    const int cfg = env_int("BAGUA_RESIDENT_CFG", kResDefaultCfg);
+    const int cfg = env_int("BAGUA_RESIDENT_CFG", resident_default_cfg<T>());
     if (env_int("BAGUA_RESIDENT", 1) == 0 || cfg < 0 || cfg >= kResNumCfg || p <= 0) return pl;
     {
         std::lock_guard<std::mutex> lk(g_res_mu);
@@ -820,8 +1172,13 @@ int resident_compress_impl(const void* input, int64_t in_num_elem, int64_t cs, i
 #define BAGUA_RES_LAUNCH(I)                                                                                 \
     case I: {                                                                                               \
         constexpr ResidentCfg k = kResCfg[I];                                                               \
-        launch(minmax_resident_encode_kernel<T, k.block, k.r, k.h, k.sb, k.ntm>, dim3(a.grid), dim3(k.block),     \
-               (uint32_t)pl.lds, s, a);                                                                     \
+        if constexpr (k.stack != 0)                                                                         \
+            launch(minmax_resident_encode_kernel_stack<T, k.block, k.r, k.h, k.sb, k.ntm, (k.stack & 2) != 0, \
+                                                       (k.stack & 4) != 0>,                                 \
+                   dim3(a.grid), dim3(k.block), (uint32_t)pl.lds, s, a);                                    \
+        else                                                                                                \
+            launch(minmax_resident_encode_kernel<T, k.block, k.r, k.h, k.sb, k.ntm>, dim3(a.grid),          \
+                   dim3(k.block), (uint32_t)pl.lds, s, a);                                                  \
         break;                                                                                              \
     }
         BAGUA_RES_LAUNCH(0)
@@ -838,6 +1195,22 @@ int resident_compress_impl(const void* input, int64_t in_num_elem, int64_t cs, i
         BAGUA_RES_LAUNCH(11)
         BAGUA_RES_LAUNCH(12)
         BAGUA_RES_LAUNCH(13)
+        BAGUA_RES_LAUNCH(14)
+        BAGUA_RES_LAUNCH(15)
+        BAGUA_RES_LAUNCH(16)
+        BAGUA_RES_LAUNCH(17)
+        BAGUA_RES_LAUNCH(18)
+        BAGUA_RES_LAUNCH(19)
+        BAGUA_RES_LAUNCH(20)
+        BAGUA_RES_LAUNCH(21)
+        BAGUA_RES_LAUNCH(22)
+        BAGUA_RES_LAUNCH(23)
+        BAGUA_RES_LAUNCH(24)
+        BAGUA_RES_LAUNCH(25)
+        BAGUA_RES_LAUNCH(26)
+        BAGUA_RES_LAUNCH(27)
+        BAGUA_RES_LAUNCH(28)
+        BAGUA_RES_LAUNCH(29)
 #undef BAGUA_RES_LAUNCH
         default:
             return BAGUA_ERR_UNSUPPORTED;  // a configuration without a launch: never silently skip the encode
@@ -963,6 +1336,44 @@ extern "C" int bagua_minmax_u8_resident_path(int dtype, const void* input, int i
     return 0;
 }
 
-namespace bagua {
+extern "C" int bagua_minmax_u8_resident_default_cfg(int dtype) {
+    using namespace bagua;
+    switch (dtype) {
+        case BAGUA_DTYPE_F32: return resident_default_cfg<F32>();
+        case BAGUA_DTYPE_F16: return resident_default_cfg<F16>();
+        case BAGUA_DTYPE_BF16: return resident_default_cfg<BF16>();
+    }
+    return -1;
+}
 
-}  // namespace bagua
+extern "C" int bagua_minmax_u8_resident_cfg_geometry(int cfg, int* block, int* r, int* h, int* sb, int* stack) {
+    using namespace bagua;
+    if (cfg < 0 || cfg >= kResNumCfg || !block || !r || !h || !sb || !stack) return BAGUA_ERR_INVALID_ARG;
+    *block = kResCfg[cfg].block;
+    *r = kResCfg[cfg].r;
+    *h = kResCfg[cfg].h;
+    *sb = kResCfg[cfg].sb;
+    *stack = kResCfg[cfg].stack;
+    return BAGUA_OK;
+}
+
+extern "C" int bagua_minmax_u8_resident_cfg_info(int dtype, int cfg, int* num_regs, int* scratch_bytes) {
+    using namespace bagua;
+    if (!num_regs || !scratch_bytes) return BAGUA_ERR_INVALID_ARG;
+    if (cfg < 0) cfg = bagua_minmax_u8_resident_default_cfg(dtype);
+    void* kern = nullptr;
+    switch (dtype) {
+        case BAGUA_DTYPE_F32: kern = resident_kernel_for<F32>(cfg); break;
+        case BAGUA_DTYPE_F16: kern = resident_kernel_for<F16>(cfg); break;
+        case BAGUA_DTYPE_BF16: kern = resident_kernel_for<BF16>(cfg); break;
+    }
+    if (!kern) return BAGUA_ERR_INVALID_ARG;
+    hipFuncAttributes attr{};
+    if (hipFuncGetAttributes(&attr, kern) != hipSuccess) {
+        g_last_hip_error = (int)hipGetLastError();
+        return BAGUA_ERR_HIP;
+    }
+    *num_regs = attr.numRegs;
+    *scratch_bytes = (int)attr.localSizeBytes;
+    return BAGUA_OK;
+}

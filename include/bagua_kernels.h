@@ -95,7 +95,9 @@ int bagua_minmax_u8_resident_path(int dtype, const void* input, int input_num_el
 /* Measurement hook: while set, every one-launch encode writes wall_clock64
  * stamps into `device_buffer` (>= 8 * CU count u64), 8 slots per workgroup:
  * start, end of pass 1, exchange done, end of pass 2, end of the streamed
- * part of pass 2, end of its LDS part.  NULL disarms. */
+ * part of pass 2, end of its LDS part; the stack-order rows leave slots 4 and 5
+ * alone and write slot 6 (held rows stored) and slot 7 (parked rows stored)
+ * instead, their pass 2 running in that order.  NULL disarms. */
 int bagua_minmax_u8_resident_trace(void* device_buffer);
 /* The one-launch encode keeps a small device slot per stream (its ticket
  * counter and min/max exchange granules; 64 per device).  hipStreamPerThread
@@ -114,6 +116,19 @@ int bagua_minmax_u8_resident_slots_in_use(int device_id);
  * for their chunk's partials (contention with other streams' kernels) and re-read the
  * missing slices instead.  Synchronises `stream`. */
 int bagua_minmax_u8_resident_give_ups(bagua_stream_t stream, uint64_t* count);
+/* The one-launch encode's kernel configuration table (minmax_resident.hip kResCfg):
+ * the row compress calls use for `dtype` unless BAGUA_RESIDENT_CFG names another; -1
+ * for an unknown dtype. */
+int bagua_minmax_u8_resident_default_cfg(int dtype);
+/* Row `cfg`: threads per workgroup, vectors per lane held in VGPRs (R) and parked in
+ * LDS (H), vectors per lane per streamed tile (SB), and whether the row runs the
+ * stack-order kernel (0 no, 1 yes, 2 with its first tile requested before the ticket). */
+int bagua_minmax_u8_resident_cfg_geometry(int cfg, int* block, int* r, int* h, int* sb, int* stack);
+/* Spill guard: the registers per lane and the scratch (private segment) bytes per lane
+ * of row `cfg`'s kernel for `dtype`, as the loaded code object reports them
+ * (hipFuncGetAttributes).  cfg < 0: the dtype's default row.  No shipped default may
+ * use scratch: tests assert scratch_bytes == 0. */
+int bagua_minmax_u8_resident_cfg_info(int dtype, int cfg, int* num_regs, int* scratch_bytes);
 /* decompress_uint8_to_{f32,f16}_host (K:667-681) */
 int bagua_minmax_u8_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
                                int num_chunks, void* output, bagua_stream_t stream);

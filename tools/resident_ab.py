@@ -6,6 +6,9 @@ order, so box and clock drift hit every build alike.
   python tools/resident_ab.py --lib r01=ab_libs/r01/libbagua_kernels.so \
       --lib head=bagua-core_amd/lib/libbagua_kernels.so [--rounds 8 --steps 40]
 
+A build given as name=path@CFG runs with BAGUA_RESIDENT_CFG=CFG (one library may appear
+under several names, one per kernel configuration); without @CFG it runs its default.
+
 Per build: every encode and decode launch is timed by the kernel's own HIP
 events (bagua_time_next_kernel -> hipExtLaunchKernel, no dispatch gap), so the
 output has the per-launch distribution (mean, p50, p90, max) and the step wall
@@ -68,11 +71,20 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--onebit", action="store_true", help="the 1-bit codec (config 3) instead of MinMax")
     a = ap.parse_args()
-    libs = []
+    libs, cfgs = [], {}
+
+    def select(name):  # the build's kernel configuration, read by the library at every call
+        if cfgs[name]:
+            os.environ["BAGUA_RESIDENT_CFG"] = cfgs[name]
+        else:
+            os.environ.pop("BAGUA_RESIDENT_CFG", None)
+
     for spec in a.lib:
         name, path = spec.split("=", 1)
+        path, _, cfg = path.partition("@")
         L, gu = load(path)
         libs.append((name, L, gu))
+        cfgs[name] = cfg
     n = a.elements
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0x5EED)
@@ -101,6 +113,7 @@ def main():
     torch.cuda.synchronize()
     ref = None
     for name, L, _ in libs:  # every build must produce the same bytes
+        select(name)
         assert enc(L) == 0
         torch.cuda.synchronize()
         h = comp.cpu()
@@ -137,6 +150,7 @@ def main():
     for r in range(a.rounds):
         order = libs if r % 2 == 0 else libs[::-1]
         for name, L, gu in order:
+            select(name)
             run(L, 5, False)
             wall, _, _ = run(L, a.steps, False)
             _, te, td = run(L, a.steps, True)
@@ -156,6 +170,7 @@ def main():
         print(json.dumps(out), flush=True)
     if a.trace and not a.onebit:
         name, L, gu = libs[-1]
+        select(name)
         cus = torch.cuda.get_device_properties(dev).multi_processor_count
         steps = a.steps * 2
         tr = torch.zeros(steps, 8 * cus, dtype=torch.int64, device=dev)

@@ -62,17 +62,24 @@ def main():
         t = np.stack(rows)  # runs x wg x 8
         if a.dump:
             np.save(a.dump.replace(".npy", f"_cfg{cfg}.npy"), t)
+        geo = [ctypes.c_int(0) for _ in range(5)]
+        N.check(K.bagua_minmax_u8_resident_cfg_geometry(cfg, *[ctypes.byref(g) for g in geo]), "cfg geometry")
+        stack = geo[4].value != 0
+        # stack-order rows run pass 2 as held rows (stamp 6), parked rows (stamp 7), streamed part (end)
+        p2 = ({"pass2_regs_us": t[:, :, 6] - t[:, :, 2], "pass2_lds_us": t[:, :, 7] - t[:, :, 6],
+               "pass2_stream_us": t[:, :, 3] - t[:, :, 7]} if stack else
+              {"pass2_stream_us": t[:, :, 4] - t[:, :, 2], "pass2_lds_us": t[:, :, 5] - t[:, :, 4],
+               "pass2_regs_us": t[:, :, 3] - t[:, :, 5]})
         out = {
             "cfg": cfg,
+            "order": "stack" if stack else "stream-first",
             "start_spread_us": float(np.median(t[:, :, 0].max(axis=1))),
             "pass1_us_median_wg": float(np.median(t[:, :, 1] - t[:, :, 0])),
             "pass1_end_max_us": float(np.median(t[:, :, 1].max(axis=1))),
             "exchange_us_median_wg": float(np.median(t[:, :, 2] - t[:, :, 1])),
             "exchange_end_max_us": float(np.median(t[:, :, 2].max(axis=1))),
             "pass2_us_median_wg": float(np.median(t[:, :, 3] - t[:, :, 2])),
-            "pass2_stream_us": float(np.median(t[:, :, 4] - t[:, :, 2])),
-            "pass2_lds_us": float(np.median(t[:, :, 5] - t[:, :, 4])),
-            "pass2_regs_us": float(np.median(t[:, :, 3] - t[:, :, 5])),
+            **{k: float(np.median(v)) for k, v in p2.items()},
             "end_max_us": float(np.median(t[:, :, 3].max(axis=1))),
         }
         print(json.dumps(out), flush=True)
