@@ -22,6 +22,15 @@ REFERENCE_KERNEL_FFI = [
     "decompress_uint8_to_f16_host", "array_min_max_size_f32_host", "array_min_max_size_f16_host",
     "async_model_average_host",
 ]
+# the v1-style extensions of include/bagua_kernels.h (bf16 and the 1-bit codec under the
+# reference's naming convention; called in tests/test_gpu_v1_exports.py)
+V1_EXTENSIONS = [
+    "compress_bf16_to_uint8_host", "decompress_uint8_to_bf16_host", "array_min_max_size_bf16_host",
+    "reduce_mean_bf16_inplace_host", "reduce_sum_bf16_inplace_host", "add_inplace_bf16_host",
+    "addmul_inplace_bf16_host", "compress_f32_to_onebit_host", "decompress_onebit_to_f32_host",
+    "compress_bf16_to_onebit_host", "decompress_onebit_to_bf16_host", "onebit_temp_size_host",
+    "array_min_max_size_f16_host",
+]
 # bagua-core-c/src/lib.rs:9-69 (exported unmangled here)
 REFERENCE_C_SHIM = ["bagua_single_communicator_c_create", "bagua_single_communicator_c_destroy",
                     "bagua_single_communicator_c_nranks"]
@@ -62,6 +71,7 @@ def test_reference_ffi_names_present(built):
     k = exported(os.path.join(LIB, "libbagua_kernels.so"))
     c = exported(os.path.join(LIB, "libbagua_core.so"))
     assert not [n for n in REFERENCE_KERNEL_FFI if n not in k]
+    assert not [n for n in V1_EXTENSIONS if n not in k]
     assert not [n for n in REFERENCE_C_SHIM if n not in c]
 
 
