@@ -9,6 +9,8 @@
 //  f32 addmul: nvcc contracts `x += y*factor` (-fmad=true) -> fmaf(y, factor, x)
 //  f16: __hadd/__hmul/__hsub are correctly rounded half ops == one float op +
 //       RNE to half (24 >= 2*11+2); bf16 follows the same rule (extension).
+//  16-bit addmul: x + half(y * half(factor)); the product keeps the sign of an exact zero
+//       (apply<.., SCALAR>, tests/test_gpu_elementwise_edges.py).
 //  f16 average: __hadd(a,b) / half(2) (K:53-61) -> half(half(a+b) / 2).
 //  f16 divide: the reference's __hdiv uses an approximate reciprocal; here it
 //       is the correctly rounded quotient (parity unpinned, off the hot path).
@@ -19,7 +21,12 @@ namespace bagua {
 
 enum class Op { Add, AddMul, Sub, Avg, Div };
 
-template <typename T, Op OP>
+// SCALAR: the element-by-element loops.  There the f16 product is kept in a register of its
+// own before it is rounded: left to itself the compiler selects one v_fma_mixlo_f16 with a +0
+// addend for `half(y * f)`, and (-0) + (+0) = +0, so an exactly zero negative product (y = -0,
+// or f = 0 and y < 0) lost its sign and -0 + y * f came out +0.  The vector loop is not
+// affected (v_pk_mul_f32, then v_cvt_pk_f16_f32) and stays as it was.
+template <typename T, Op OP, bool SCALAR = false>
 __device__ __forceinline__ float apply(float x, float y, float f) {
     if constexpr (OP == Op::Add) return x + y;
     if constexpr (OP == Op::Sub) return x - y;
@@ -30,7 +37,9 @@ __device__ __forceinline__ float apply(float x, float y, float f) {
     }
     if constexpr (OP == Op::AddMul) {
         if constexpr (sizeof(typename T::storage) == 4) return __builtin_fmaf(y, f, x);
-        return x + T::to_f(T::from_f(y * f));  // f is already rounded to T by the launcher
+        float prod = y * f;  // f is already rounded to T by the launcher
+        if constexpr (SCALAR) asm volatile("" : "+v"(prod));
+        return x + T::to_f(T::from_f(prod));
     }
     return x;
 }
@@ -56,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void binary_kernel(typename T::storage* __r
         done = nvec * N;
     }
     for (int64_t i = done + tid; i < n; i += stride)
-        x[i] = T::from_f(apply<T, OP>(T::to_f(x[i]), OP == Op::Div ? 0.0f : T::to_f(y[i]), f));
+        x[i] = T::from_f(apply<T, OP, true>(T::to_f(x[i]), OP == Op::Div ? 0.0f : T::to_f(y[i]), f));
 }
 
 template <typename T, Op OP>
