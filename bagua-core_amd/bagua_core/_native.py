@@ -99,6 +99,7 @@ KERNEL_SIGNATURES = {
     "bagua_minmax_u8_resident_give_ups": (_i32, [_vp, ctypes.POINTER(_u64)]),
     "bagua_minmax_u8_resident_default_cfg": (_i32, [_i32]),
     "bagua_minmax_u8_resident_cfg_geometry": (_i32, [_i32] + [ctypes.POINTER(_i32)] * 5),
+    "bagua_minmax_u8_resident_cfg_order": (_i32, [_i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "bagua_minmax_u8_resident_cfg_info": (_i32, [_i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "bagua_minmax_u8_decompress_reduce": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _vp]),
     "bagua_minmax_u8_reduce_requantize": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _vp, _sz, _i32, _vp, _sz,

@@ -21,10 +21,13 @@
 //           read last are the ones the 256 MiB Infinity Cache still holds),
 //           then the LDS part, then the VGPR part, and write header / slack.
 //
-// minmax_resident_encode_kernel_stack (the f32 and f16 default) runs the passes in
+// minmax_resident_encode_kernel_stack (the f16 default) runs the passes in
 // stack order instead -- pass 1: streamed, parked, held; pass 2: held, parked,
 // streamed -- so the held vectors reuse the streaming buffers' registers and more
 // of the chunk stays on chip without scratch (see the comment above that kernel).
+// minmax_resident_encode_kernel_window (the f32 and bf16 default) keeps the order above
+// and loads a last few held rows into the streaming buffers' registers once pass 1 has
+// streamed, so as much stays on chip and the re-read follows the read closely.
 //
 // Per-launch state lives in a library-owned slot (one per stream; the
 // hipStreamPerThread sentinel gets one per host thread) that is never reset:
@@ -785,10 +788,284 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
         __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Window order: the stream-last order of minmax_resident_encode_kernel, with the stack
+// trick applied to the streaming buffers' registers only.  A slice is rows [0, RE) held
+// early in VGPRs, rows [RE, RE + H) parked in LDS, rows [RE + H, RE + H + RL) held late,
+// the rest streamed:
+//
+//   pass 1: the early rows, the parked rows, the streamed rows (ascending,
+//           double-buffered), then the late rows, loaded into the registers the
+//           streaming buffers no longer need
+//   pass 2: the late rows first (their registers become pass 2's tile buffers), then
+//           the streamed rows from the top down, requested as soon as the late rows are
+//           stored, then the parked rows, then the early rows.
+//
+// Between a streamed row's read and its re-read only the late rows' loads and stores go
+// by (the stack order puts the whole on-chip part there), so the re-read finds more of
+// its lines in the Infinity Cache; the register budget is
+// 4 RE + max(streaming buffers, 4 RL) + temporaries.  Slice ownership, scalars, header
+// and slack, the exchange, the give-up path, tickets and the drain counter are those of
+// minmax_resident_encode_kernel.
+// Trace stamps: 0 start, 1 pass 1 end, 2 exchange end, 6 late rows stored, 4 streamed
+// rows stored, 5 parked rows stored, 3 end.
+template <typename T, int BLOCK, int RE, int H, int RL, int SB, int NTM>
+__global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_window(ResidentArgs a) {
+    constexpr int N = Vec<T>::N;
+    constexpr bool NT = (NTM & 1) != 0;
+    constexpr bool NT1 = (NTM & 2) != 0;
+    constexpr int W = BLOCK / kWave;
+    static_assert(RE > 0 && H > 0 && RL > 0, "the window order keeps rows in VGPRs (early and late) and in LDS");
+    extern __shared__ __attribute__((aligned(16))) uint4 smem[];
+    uint4* park = smem;
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // 2*W + 4 words
+    const int t = (int)threadIdx.x;
+    const int g = (int)blockIdx.x;
+
+    const int lane_c = g % kResLanes;
+    if (t == 0) {
+        const uint64_t ticket = __hip_atomic_fetch_add(&a.slot->ticket[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_AGENT);
+        scratch[2 * W] = tag_of_ticket(ticket, a.grid, lane_c);
+    }
+    __syncthreads();
+    const uint32_t tag = scratch[2 * W];
+    trace_stamp(a, g, 0);
+    if (g >= a.nact * a.bpc) {  // idle: the grid is the CU count on every launch of the slot
+        if (t == 0)
+            __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+
+    const SliceGeom<T, BLOCK> s(a, g);
+    const uint4* __restrict__ v = reinterpret_cast<const uint4*>(s.src + s.j0);
+    const int64_t v0 = s.v0, v1 = s.v1;
+    const int64_t vl = v1 - 1;                                   // clamp target (used only when v1 > v0)
+    const int64_t stream0 = v0 + (int64_t)(RE + H + RL) * BLOCK;  // first streamed vector
+    const int64_t tile = (int64_t)SB * BLOCK;
+    const int64_t nfull = v1 > stream0 ? (v1 - stream0) / tile : 0;
+    const int64_t top = stream0 + nfull * tile;  // the ragged top tile [top, v1), possibly empty
+
+    // ---- pass 1 ------------------------------------------------------------
+    uint32_t lo = min_space(T::init_max());
+    uint32_t hi = max_space(-T::init_max());
+    uint4 held[RE], late[RL];
+    if (v1 > v0) {
+#pragma unroll
+        for (int k = 0; k < RE; ++k) {
+            const int64_t i = v0 + (int64_t)k * BLOCK + t;
+            held[k] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
+        }
+        // software-pipelined as in minmax_resident_encode_kernel: the next batch of parked
+        // rows is in flight while the current one (first: the early rows) is folded
+        uint4 cur[SB], nxt[SB];
+#pragma unroll
+        for (int j = 0; j < SB; ++j) {
+            if (j < H) {
+                const int64_t i = v0 + (int64_t)(RE + j) * BLOCK + t;
+                cur[j] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < RE; ++k) {
+            fold_vec<T>(held[k], lo, hi);
+            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // four rows' keys at a time
+        }
+#pragma unroll
+        for (int kb = 0; kb < H; kb += SB) {
+#pragma unroll
+            for (int j = 0; j < SB; ++j) {
+                if (kb + SB + j < H) {
+                    const int64_t i = v0 + (int64_t)(RE + kb + SB + j) * BLOCK + t;
+                    nxt[j] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < SB; ++j) {
+                if (kb + j < H) {
+                    fold_vec<T>(cur[j], lo, hi);
+                    park[(kb + j) * BLOCK + t] = cur[j];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < SB; ++j) cur[j] = nxt[j];
+        }
+        // streamed rows: full tiles double-buffered, then the ragged top tile (clamped)
+        uint4 ra[SB], rb[SB];
+        if (nfull > 0) {
+            load_tile<SB, BLOCK>(v, stream0, t, ra);
+            for (int64_t i = 0; i < nfull; i += 2) {
+                // unconditional (clamped) prefetches keep the wait counts static
+                load_tile<SB, BLOCK>(v, stream0 + (i + 1 < nfull ? i + 1 : nfull - 1) * tile, t, rb);
+#pragma unroll
+                for (int j = 0; j < SB; ++j) fold_vec<T>(ra[j], lo, hi);
+                load_tile<SB, BLOCK>(v, stream0 + (i + 2 < nfull ? i + 2 : nfull - 1) * tile, t, ra);
+                if (i + 1 < nfull) {
+#pragma unroll
+                    for (int j = 0; j < SB; ++j) fold_vec<T>(rb[j], lo, hi);
+                }
+            }
+        }
+        if (v1 > top) {
+            load_tile_clamped<SB, BLOCK, false>(v, top, vl, t, rb);
+#pragma unroll
+            for (int j = 0; j < SB; ++j) fold_vec<T>(rb[j], lo, hi);
+        }
+        // the late rows, last: every streaming buffer above is dead.  The scheduling
+        // barriers keep it so (see minmax_resident_encode_kernel_stack).
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < RL; ++k) {
+            const int64_t i = v0 + (int64_t)(RE + H + k) * BLOCK + t;
+            late[k] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < RL; ++k) {
+            fold_vec<T>(late[k], lo, hi);
+            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if (s.last) fold_scalars<T, BLOCK>(a, s, lo, hi);
+    lo = wave_umin(lo);
+    hi = wave_umin(hi);
+    const int w = t / kWave;
+    if (lane_id() == 0) { scratch[w] = lo; scratch[W + w] = hi; }
+    __syncthreads();
+    if (t == 0) {
+#pragma unroll
+        for (int i = 1; i < W; ++i) { lo = min(lo, scratch[i]); hi = min(hi, scratch[W + i]); }
+        uint64_t* mine = a.slot->gran + 2 * (int64_t)g;
+        __hip_atomic_store(mine, ((uint64_t)tag << 32) | lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mine + 1, ((uint64_t)tag << 32) | hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    trace_stamp(a, g, 1);
+
+    // ---- exchange ------------------------------------------------------------
+    if (w == 0) {
+        const uint64_t deadline = wall_clock64() + a.timeout_ticks;
+        uint32_t l = 0, h = 0;
+        const bool ok = sweep_chunk(a, s.cl, tag, deadline, l, h, true);
+        if (lane_id() == 0) {
+            scratch[2 * W + 1] = ok ? 1u : 0u;
+            scratch[2 * W + 2] = l;
+            scratch[2 * W + 3] = h;
+        }
+    }
+    __syncthreads();
+    if (scratch[2 * W + 1] == 0u) {
+        // gave up waiting: the whole workgroup folds the missing slices itself
+        if (t == 0) __hip_atomic_fetch_add(&a.slot->gave_up, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t l = 0xffffffffu, h = 0xffffffffu;
+        fold_missing_slices<T, BLOCK, true>(a, s.cl, tag, l, h);
+        l = wave_umin(l);
+        h = wave_umin(h);
+        if (lane_id() == 0) { scratch[w] = l; scratch[W + w] = h; }
+        __syncthreads();
+        if (t == 0) {
+#pragma unroll
+            for (int i = 1; i < W; ++i) { l = min(l, scratch[i]); h = min(h, scratch[W + i]); }
+            scratch[2 * W + 2] = l;
+            scratch[2 * W + 3] = h;
+        }
+        __syncthreads();
+    }
+    const float mn = from_min_space(scratch[2 * W + 2]), mx = from_max_space(scratch[2 * W + 3]);
+    const QParams q = make_qparams(mn, mx);
+    trace_stamp(a, g, 2);
+
+    // ---- pass 2 ------------------------------------------------------------
+    write_extras<T, BLOCK>(a, s, mn, mx, q);
+    uint8_t* vdst = s.payload + s.j0;
+    const bool whole = stream0 <= v1;  // the whole on-chip part is inside the slice: no per-vector guards
+    uint8_t* vd = vdst + (v0 + t) * N;
+    // a short slice's guard: its vector count against the lane's offset, in 32 bits
+    constexpr int kOnChip = (RE + H + RL) * BLOCK;
+    const int nloc = (int)(v1 - v0 < (int64_t)kOnChip ? (v1 > v0 ? v1 - v0 : 0) : (int64_t)kOnChip);
+    if (whole) {
+#pragma unroll
+        for (int k = 0; k < RL; ++k) {
+            quant_store<T>(late[k], q, vd + (int64_t)(RE + H + k) * BLOCK * N);
+            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // four rows' temporaries at a time
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < RL; ++k)
+            if ((RE + H + k) * BLOCK + t < nloc) quant_store<T>(late[k], q, vd + (int64_t)(RE + H + k) * BLOCK * N);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // no streamed tile is requested while late rows are live
+    trace_stamp(a, g, 6);
+    // the two top streamed tiles (the ragged one, then the top full one) are requested now
+    // (buffers of their own: pass 1's would count as live across the exchange)
+    {
+        uint4 qa[SB], qb[SB];
+        if (v1 > top) load_tile_clamped<SB, BLOCK, NT>(v, top, vl, t, qb);
+        if (nfull > 0) load_tile<SB, BLOCK, NT>(v, stream0 + (nfull - 1) * tile, t, qa);
+        if (v1 > top) {
+#pragma unroll
+            for (int j = 0; j < SB; ++j) {
+                const int64_t i = top + j * BLOCK + t;
+                if (i < v1) quant_store<T>(qb[j], q, vdst + i * N);
+            }
+        }
+        if (nfull > 0) {
+            // full tiles double-buffered from the top down (what pass 1 read last of the
+            // streamed part is re-read first)
+            for (int64_t i = nfull - 1; i >= 0; i -= 2) {
+                load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 1 ? i - 1 : 0) * tile, t, qb);
+                const int64_t ba = stream0 + i * tile;
+#pragma unroll
+                for (int j = 0; j < SB; ++j) quant_store<T>(qa[j], q, vdst + (ba + j * BLOCK + t) * N);
+                load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 2 ? i - 2 : 0) * tile, t, qa);
+                if (i >= 1) {
+                    const int64_t bb = ba - tile;
+#pragma unroll
+                    for (int j = 0; j < SB; ++j) quant_store<T>(qb[j], q, vdst + (bb + j * BLOCK + t) * N);
+                }
+            }
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    trace_stamp(a, g, 4);
+    if (whole) {
+#pragma unroll
+        for (int kb = 0; kb < H; kb += SB) {
+            uint4 r[SB];
+#pragma unroll
+            for (int j = 0; j < SB; ++j)
+                if (kb + j < H) r[j] = park[(kb + j) * BLOCK + t];
+#pragma unroll
+            for (int j = 0; j < SB; ++j)
+                if (kb + j < H) quant_store<T>(r[j], q, vd + (int64_t)(RE + kb + j) * BLOCK * N);
+        }
+        trace_stamp(a, g, 5);
+#pragma unroll
+        for (int k = 0; k < RE; ++k) {
+            quant_store<T>(held[k], q, vd + (int64_t)k * BLOCK * N);
+            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < H; ++k)
+            if ((RE + k) * BLOCK + t < nloc) quant_store<T>(park[k * BLOCK + t], q, vd + (int64_t)(RE + k) * BLOCK * N);
+        trace_stamp(a, g, 5);
+#pragma unroll
+        for (int k = 0; k < RE; ++k)
+            if (k * BLOCK + t < nloc) quant_store<T>(held[k], q, vd + (int64_t)k * BLOCK * N);
+    }
+    if (a.trace != nullptr) {
+        __syncthreads();
+        trace_stamp(a, g, 3);
+    }
+    // counted last, as in minmax_resident_encode_kernel
+    if (t == 0)
+        __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------
-// Slot keys.  hipStreamPerThread is a sentinel that names a DIFFERENT real
+// Slot keys. hipStreamPerThread is a sentinel that names a DIFFERENT real
 // stream on every host thread, so two threads launching on it must not share a
 // slot (their tickets and granules would interleave): the sentinel is keyed
 // together with the calling thread.  Every other handle is one stream.
@@ -842,6 +1119,8 @@ struct ResidentCfg {
     int ntm;    // non-temporal loads: bit 0 pass-2 re-reads, bit 1 pass-1 loads of the on-chip part
     int stack;  // bit 0: minmax_resident_encode_kernel_stack (stack-order passes); bit 1: its first tile
                 // requested before the ticket; bit 2: pass 2 re-reads the streamed tiles bottom-up
+    int rl;     // > 0: minmax_resident_encode_kernel_window (window order) with r rows held early and
+                // rl rows held late
 };
 static constexpr ResidentCfg kResCfg[] = {
     {256, 32, 39, 8, 0},   // 0
@@ -876,8 +1155,14 @@ static constexpr ResidentCfg kResCfg[] = {
     {512, 48, 19, 4, 3, 5},  // 27: 18 bottom-up
     {512, 44, 19, 4, 3, 5},  // 28
     {512, 44, 19, 4, 3, 1},  // 29
+    {512, 44, 19, 4, 3, 0},  // 30: stream-last (as 12) at R = 44, SB = 4: the window rows' control
+    // window order (minmax_resident_encode_kernel_window): r rows held early, rl rows held late in
+    // the streaming buffers' registers; non-temporal as in 12
+    {512, 44, 19, 4, 3, 0, 8},   // 31: 52 rows in VGPRs (f32 and f16 spill: not candidates there)
+    {512, 40, 19, 4, 3, 0, 12},  // 32: 52 rows in VGPRs without scratch for f32 and bf16
 };
 constexpr int kResNumCfg = (int)(sizeof(kResCfg) / sizeof(kResCfg[0]));
+static_assert(kResCfg[29].rl == 0 && kResCfg[31].rl == 8 && kResCfg[32].rl == 12, "row numbers are named by BAGUA_RESIDENT_CFG and the tests");
 // 12: config 11 with the on-chip part of pass 1 also loaded non-temporally.  The
 // one-bucket loop is unchanged (1,894-1,898 vs 1,892-1,916 GiB/s), and alternating
 // buckets -- a bucket last touched a whole other bucket ago, as in training -- gain
@@ -885,18 +1170,24 @@ constexpr int kResNumCfg = (int)(sizeof(kResCfg) / sizeof(kResCfg[0]));
 // on-chip part non-temporal with default re-reads, shortens the encode to 78-80 us
 // but slows the decode after it by as much)
 constexpr int kResDefaultCfg = 12;
-// Per dtype, from the stack-order sweep (profiles/resident_stack_ab.jsonl):
-// f32 takes 24 (R = 52, 55 % of the bucket on chip, 256 VGPRs, no scratch) and f16 takes 29
-// (R = 44: the 16-bit kernels need more temporaries); bf16 stays on 12, its best stack
-// row (18) gaining less than the run-to-run spread.  No default may use scratch
-// (bagua_minmax_u8_resident_cfg_info, test_default_rows_use_no_scratch).
+// Per dtype, from the stack-order and window-order sweeps (profiles/resident_stack_ab.jsonl,
+// profiles/resident_window_*.json*): f32 takes 32 (window order, 40 rows held
+// early + 12 late: 55 % of the bucket on chip as in 24, 256 VGPRs, no scratch, and a fresher
+// re-read), bf16 takes 31 (44 + 8, likewise) and f16 stays on 29 (stack order, R = 44: the f16
+// kernels need more temporaries; its only window row without scratch, 36 + 8, lost to 29).
+// No default may use scratch (bagua_minmax_u8_resident_cfg_info,
+// test_default_rows_use_no_scratch).
 template <typename T>
 constexpr int resident_default_cfg() {
     return kResDefaultCfg;
 }
 template <>
 constexpr int resident_default_cfg<F32>() {
-    return 24;
+    return 32;
+}
+template <>
+constexpr int resident_default_cfg<BF16>() {
+    return 31;
 }
 template <>
 constexpr int resident_default_cfg<F16>() {
@@ -910,7 +1201,9 @@ static size_t resident_lds_bytes(const ResidentCfg& c) {
 template <typename T, int CFG>
 static void* resident_kernel_ptr() {
     constexpr ResidentCfg c = kResCfg[CFG];
-    if constexpr (c.stack != 0)
+    if constexpr (c.rl != 0)
+        return reinterpret_cast<void*>(&minmax_resident_encode_kernel_window<T, c.block, c.r, c.h, c.rl, c.sb, c.ntm>);
+    else if constexpr (c.stack != 0)
         return reinterpret_cast<void*>(
             &minmax_resident_encode_kernel_stack<T, c.block, c.r, c.h, c.sb, c.ntm, (c.stack & 2) != 0, (c.stack & 4) != 0>);
     else
@@ -950,6 +1243,9 @@ static void* resident_kernel_for(int cfg) {
         case 27: return resident_kernel_ptr<T, 27>();
         case 28: return resident_kernel_ptr<T, 28>();
         case 29: return resident_kernel_ptr<T, 29>();
+        case 30: return resident_kernel_ptr<T, 30>();
+        case 31: return resident_kernel_ptr<T, 31>();
+        case 32: return resident_kernel_ptr<T, 32>();
     }
     return nullptr;
 }
@@ -1172,7 +1468,10 @@ int resident_compress_impl(const void* input, int64_t in_num_elem, int64_t cs, i
 #define BAGUA_RES_LAUNCH(I)                                                                                 \
     case I: {                                                                                               \
         constexpr ResidentCfg k = kResCfg[I];                                                               \
-        if constexpr (k.stack != 0)                                                                         \
+        if constexpr (k.rl != 0)                                                                            \
+            launch(minmax_resident_encode_kernel_window<T, k.block, k.r, k.h, k.rl, k.sb, k.ntm>,           \
+                   dim3(a.grid), dim3(k.block), (uint32_t)pl.lds, s, a);                                    \
+        else if constexpr (k.stack != 0)                                                                    \
             launch(minmax_resident_encode_kernel_stack<T, k.block, k.r, k.h, k.sb, k.ntm, (k.stack & 2) != 0, \
                                                        (k.stack & 4) != 0>,                                 \
                    dim3(a.grid), dim3(k.block), (uint32_t)pl.lds, s, a);                                    \
@@ -1211,6 +1510,9 @@ int resident_compress_impl(const void* input, int64_t in_num_elem, int64_t cs, i
         BAGUA_RES_LAUNCH(27)
         BAGUA_RES_LAUNCH(28)
         BAGUA_RES_LAUNCH(29)
+        BAGUA_RES_LAUNCH(30)
+        BAGUA_RES_LAUNCH(31)
+        BAGUA_RES_LAUNCH(32)
 #undef BAGUA_RES_LAUNCH
         default:
             return BAGUA_ERR_UNSUPPORTED;  // a configuration without a launch: never silently skip the encode
@@ -1354,6 +1656,14 @@ extern "C" int bagua_minmax_u8_resident_cfg_geometry(int cfg, int* block, int* r
     *h = kResCfg[cfg].h;
     *sb = kResCfg[cfg].sb;
     *stack = kResCfg[cfg].stack;
+    return BAGUA_OK;
+}
+
+extern "C" int bagua_minmax_u8_resident_cfg_order(int cfg, int* order, int* rl) {
+    using namespace bagua;
+    if (cfg < 0 || cfg >= kResNumCfg || !order || !rl) return BAGUA_ERR_INVALID_ARG;
+    *order = kResCfg[cfg].rl != 0 ? 2 : (kResCfg[cfg].stack != 0 ? 1 : 0);
+    *rl = kResCfg[cfg].rl;
     return BAGUA_OK;
 }
 

@@ -124,6 +124,9 @@ int bagua_minmax_u8_resident_default_cfg(int dtype);
  * LDS (H), vectors per lane per streamed tile (SB), and whether the row runs the
  * stack-order kernel (0 no, 1 yes, 2 with its first tile requested before the ticket). */
 int bagua_minmax_u8_resident_cfg_geometry(int cfg, int* block, int* r, int* h, int* sb, int* stack);
+/* Row `cfg`'s pass order: 0 stream-last (minmax_resident_encode_kernel), 1 stack order,
+ * 2 window order, whose R rows are held early and *rl more rows late (0 for the others). */
+int bagua_minmax_u8_resident_cfg_order(int cfg, int* order, int* rl);
 /* Spill guard: the registers per lane and the scratch (private segment) bytes per lane
  * of row `cfg`'s kernel for `dtype`, as the loaded code object reports them
  * (hipFuncGetAttributes).  cfg < 0: the dtype's default row.  No shipped default may

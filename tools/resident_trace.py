@@ -65,14 +65,27 @@ def main():
         geo = [ctypes.c_int(0) for _ in range(5)]
         N.check(K.bagua_minmax_u8_resident_cfg_geometry(cfg, *[ctypes.byref(g) for g in geo]), "cfg geometry")
         stack = geo[4].value != 0
-        # stack-order rows run pass 2 as held rows (stamp 6), parked rows (stamp 7), streamed part (end)
-        p2 = ({"pass2_regs_us": t[:, :, 6] - t[:, :, 2], "pass2_lds_us": t[:, :, 7] - t[:, :, 6],
-               "pass2_stream_us": t[:, :, 3] - t[:, :, 7]} if stack else
-              {"pass2_stream_us": t[:, :, 4] - t[:, :, 2], "pass2_lds_us": t[:, :, 5] - t[:, :, 4],
-               "pass2_regs_us": t[:, :, 3] - t[:, :, 5]})
+        order, rl = ctypes.c_int(0), ctypes.c_int(0)
+        N.check(K.bagua_minmax_u8_resident_cfg_order(cfg, ctypes.byref(order), ctypes.byref(rl)), "cfg order")
+        window = order.value == 2
+        # stack-order rows run pass 2 as held rows (stamp 6), parked rows (stamp 7), streamed part (end);
+        # window-order rows as late rows (stamp 6), streamed part (stamp 4), parked rows (stamp 5), early rows
+        if window:
+            p2 = {"pass2_late_us": t[:, :, 6] - t[:, :, 2], "pass2_stream_us": t[:, :, 4] - t[:, :, 6],
+                  "pass2_lds_us": t[:, :, 5] - t[:, :, 4], "pass2_regs_us": t[:, :, 3] - t[:, :, 5]}
+        elif stack:
+            p2 = {"pass2_regs_us": t[:, :, 6] - t[:, :, 2], "pass2_lds_us": t[:, :, 7] - t[:, :, 6],
+                  "pass2_stream_us": t[:, :, 3] - t[:, :, 7]}
+        else:
+            p2 = {"pass2_stream_us": t[:, :, 4] - t[:, :, 2], "pass2_lds_us": t[:, :, 5] - t[:, :, 4],
+                  "pass2_regs_us": t[:, :, 3] - t[:, :, 5]}
+        rows_total = n * 4 // 16 // cus // geo[0].value  # rows per slice (f32)
+        reread_mb = max(0, rows_total - geo[1].value - geo[2].value - rl.value) * geo[0].value * 16 * cus / 1e6
         out = {
             "cfg": cfg,
-            "order": "stack" if stack else "stream-first",
+            "order": "window" if window else ("stack" if stack else "stream-first"),
+            "r": geo[1].value, "h": geo[2].value, "rl": rl.value, "sb": geo[3].value,
+            "reread_mb": round(reread_mb, 1),
             "start_spread_us": float(np.median(t[:, :, 0].max(axis=1))),
             "pass1_us_median_wg": float(np.median(t[:, :, 1] - t[:, :, 0])),
             "pass1_end_max_us": float(np.median(t[:, :, 1].max(axis=1))),
@@ -82,6 +95,8 @@ def main():
             **{k: float(np.median(v)) for k, v in p2.items()},
             "end_max_us": float(np.median(t[:, :, 3].max(axis=1))),
         }
+        if reread_mb > 0:
+            out["pass2_stream_us_per_100mb"] = round(out["pass2_stream_us"] / reread_mb * 100, 2)
         print(json.dumps(out), flush=True)
 
 
