@@ -29,6 +29,15 @@
 // and loads a last few held rows into the streaming buffers' registers once pass 1 has
 // streamed, so as much stays on chip and the re-read follows the read closely.
 //
+// Layout of this file: the launch arguments and slice geometry; the per-vector and
+// per-chunk pieces (fold_vec, write_extras, sweep_chunk, fold_missing_slices); the shared
+// phases, each written once as a forced-inline template over the caller's register arrays
+// (draw_tag, load_rows, fold_rows, fold_and_park, fold_stream_ascending, publish_partials,
+// exchange_minmax, quant_rows, quant_parked, quant_top_tile, quant_stream_descending /
+// _ascending, finish); the three kernels, each a sequence of those phases in its own order
+// with its own scheduling barriers and trace stamps; then the host side: slots, kResCfg,
+// one table of kernel pointers per dtype built from kResCfg, the launch plan and the C ABI.
+//
 // Per-launch state lives in a library-owned slot (one per stream; the
 // hipStreamPerThread sentinel gets one per host thread) that is never reset:
 // launch k on a slot draws tickets [kG, (k+1)G) from monotonic counters, so
@@ -270,35 +279,341 @@ __device__ void fold_missing_slices(const ResidentArgs& a, int cl, uint32_t tag,
     }
 }
 
-// NTM: non-temporal load mask -- bit 0: pass 2's re-reads of the streamed part;
-// bit 1: pass 1's loads of the part kept on chip (held in VGPRs / parked in LDS), which
-// nothing re-reads, so they need not take Infinity-Cache lines from the streamed part
-template <typename T, int BLOCK, int R, int H, int SB, int NTM>
-__global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(ResidentArgs a) {
-    constexpr int N = Vec<T>::N;
-    constexpr bool NT = (NTM & 1) != 0;
-    constexpr bool NT1 = (NTM & 2) != 0;
-    constexpr int W = BLOCK / kWave;
-    // dynamic LDS only (guide Guideline 17): [H * BLOCK parked vectors][scratch]
-    extern __shared__ __attribute__((aligned(16))) uint4 smem[];
-    uint4* park = smem;
-    uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // 2*W + 4 words
-    const int t = (int)threadIdx.x;
-    const int g = (int)blockIdx.x;
+// ------------------------------------------------------------------------
+// shared phases
+// ------------------------------------------------------------------------
+// Each phase of the encode is written once here; the three kernels below are sequences of
+// these calls in their own order.  Every phase is forced inline and works on the caller's
+// register arrays (uint4 (&)[M]), so a kernel decides which registers a phase uses and when
+// they die; no phase knows which kernel calls it.  A row is BLOCK vectors, one per lane.
+//
+// The words after the parked rows in LDS (`scratch`, W = BLOCK / kWave): [0, W) per-wave min
+// keys, [W, 2W) per-wave max keys, 2W the launch's tag, 2W + 1 whether the exchange completed,
+// 2W + 2 and 2W + 3 the chunk's min and max keys.
 
-    const int lane_c = g % kResLanes;
+// the workgroup's ticket on counter `lane_c` of its slot, as the launch's tag (the same in
+// every thread)
+template <int BLOCK>
+__device__ __forceinline__ uint32_t draw_tag(const ResidentArgs& a, int lane_c, int t, uint32_t* scratch) {
+    constexpr int W = BLOCK / kWave;
     if (t == 0) {
         const uint64_t ticket = __hip_atomic_fetch_add(&a.slot->ticket[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
                                                        __HIP_MEMORY_SCOPE_AGENT);
         scratch[2 * W] = tag_of_ticket(ticket, a.grid, lane_c);
     }
     __syncthreads();
-    const uint32_t tag = scratch[2 * W];
+    return scratch[2 * W];
+}
+
+// the workgroup is done with the slot (once per workgroup, idle ones included)
+__device__ __forceinline__ void let_go_of_slot(const ResidentArgs& a, int lane_c, int t) {
+    if (t == 0)
+        __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// end of an active workgroup: stamp 3 when traced, then the workgroup lets go of the slot (its
+// granule reads ended at the exchange's barriers); counted last, so no later load waits
+// behind this atomic (on gfx9 a non-returning atomic still holds vmcnt: mid-kernel it cost
+// ~1.3 us, profiles/r03_resident_versions_ab.jsonl)
+__device__ __forceinline__ void finish(const ResidentArgs& a, int g, int lane_c, int t) {
+    if (a.trace != nullptr) {
+        __syncthreads();
+        trace_stamp(a, g, 3);
+    }
+    let_go_of_slot(a, lane_c, t);
+}
+
+// Rows [ROW0, ROW0 + K) counted from vector `base`, their indices clamped to `vl` (the
+// slice's last vector): a short slice or a ragged tile loads like a whole one, all K loads in
+// flight together and the wait counts static; a duplicate of a slice element never changes
+// the min/max, and pass 2 stores only what is in range.  The row offset is a template
+// argument so that the address folds to (base + t) + constant, as the other rows' do.
+template <int K, int ROW0, int BLOCK, bool NT, int M>
+__device__ __forceinline__ void load_rows(const uint4* v, int64_t base, int64_t vl, int t,
+                                          uint4 (&r)[M]) {
+    static_assert(K <= M, "more rows than registers");
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int64_t i = base + (int64_t)(ROW0 + k) * BLOCK + t;
+        r[k] = NT ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
+    }
+}
+
+// FENCE4: four rows' keys at a time (a scheduling barrier after every fourth row), for a
+// caller whose register budget has no room for every row's expanded keys at once
+template <typename T, int K, bool FENCE4, int M>
+__device__ __forceinline__ void fold_rows(const uint4 (&r)[M], uint32_t& lo, uint32_t& hi) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        fold_vec<T>(r[k], lo, hi);
+        if (FENCE4 && k % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// The parked rows, rows [ROW0, ROW0 + H) of the slice at vector `v0`, software-pipelined in
+// batches of SB: the next batch is in flight while the current one is folded and parked, so
+// memory never waits on VALU.  The caller requests the first batch into `cur`
+// (load_rows<min(H, SB), ROW0>) together with whatever else it wants in flight, and folds
+// that before it calls this.
+template <typename T, int BLOCK, int H, int SB, int ROW0, bool NT>
+__device__ __forceinline__ void fold_and_park(const uint4* v, int64_t v0, int64_t vl, int t,
+                                              uint4 (&cur)[SB], uint4* park, uint32_t& lo, uint32_t& hi) {
+    uint4 nxt[SB];
+#pragma unroll
+    for (int kb = 0; kb < H; kb += SB) {
+#pragma unroll
+        for (int j = 0; j < SB; ++j) {
+            if (kb + SB + j < H) {
+                const int64_t i = v0 + (int64_t)(ROW0 + kb + SB + j) * BLOCK + t;
+                nxt[j] = NT ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < SB; ++j) {
+            if (kb + j < H) {
+                fold_vec<T>(cur[j], lo, hi);
+                park[(kb + j) * BLOCK + t] = cur[j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < SB; ++j) cur[j] = nxt[j];
+    }
+}
+
+// The nfull > 0 full streamed tiles, ascending and double-buffered (2 x SB loads in flight
+// per lane: with one wave per SIMD nothing else hides the latency).  `ra` holds tile 0,
+// requested by the caller.  `last` is nfull - 1, computed by the caller next to nfull: written
+// as nfull - 1 in here, the clamp is turned into a 64-bit min before the kernel's knowledge of
+// nfull reaches it, which costs the loop six VALU instructions and three waits.
+template <typename T, int BLOCK, int SB>
+__device__ __forceinline__ void fold_stream_ascending(const uint4* v, int64_t stream0, int64_t nfull, int64_t last, int t,
+                                                      uint4 (&ra)[SB], uint4 (&rb)[SB], uint32_t& lo,
+                                                      uint32_t& hi) {
+    constexpr int64_t tile = (int64_t)SB * BLOCK;
+    for (int64_t i = 0; i < nfull; i += 2) {
+        // unconditional (clamped) prefetches keep the wait counts static
+        load_tile<SB, BLOCK>(v, stream0 + (i + 1 < nfull ? i + 1 : last) * tile, t, rb);
+        fold_rows<T, SB, false>(ra, lo, hi);
+        load_tile<SB, BLOCK>(v, stream0 + (i + 2 < nfull ? i + 2 : last) * tile, t, ra);
+        if (i + 1 < nfull) fold_rows<T, SB, false>(rb, lo, hi);
+    }
+}
+
+// every thread's keys in; the workgroup's minima out, in thread 0 only.  `w` is the thread's
+// wave, t / kWave, computed once by the kernel: a second, separately simplified copy of the
+// division keeps one more mask in SGPRs across the exchange, which spills at R = 52.
+template <int BLOCK>
+__device__ __forceinline__ void workgroup_umin(uint32_t& lo, uint32_t& hi, int t, int w, uint32_t* scratch) {
+    constexpr int W = BLOCK / kWave;
+    lo = wave_umin(lo);
+    hi = wave_umin(hi);
+    if (lane_id() == 0) { scratch[w] = lo; scratch[W + w] = hi; }
+    __syncthreads();
+    if (t == 0) {
+#pragma unroll
+        for (int i = 1; i < W; ++i) { lo = min(lo, scratch[i]); hi = min(hi, scratch[W + i]); }
+    }
+}
+
+// end of pass 1: the workgroup's {min, max} as two 8-byte {tag, value} granules
+template <int BLOCK>
+__device__ __forceinline__ void publish_partials(const ResidentArgs& a, int g, uint32_t tag, uint32_t lo, uint32_t hi,
+                                                 int t, int w, uint32_t* scratch) {
+    workgroup_umin<BLOCK>(lo, hi, t, w, scratch);
+    if (t == 0) {
+        uint64_t* mine = a.slot->gran + 2 * (int64_t)g;
+        __hip_atomic_store(mine, ((uint64_t)tag << 32) | lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mine + 1, ((uint64_t)tag << 32) | hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+struct MinMax {
+    float mn, mx;
+};
+
+// The exchange: wave 0 sweeps the granules of active chunk `cl` until every tag is this
+// launch's or the deadline passes; on a give-up the whole workgroup folds the missing slices
+// itself (fold_missing_slices; LEAN as there).  The chunk's min/max, the same in every thread.
+template <typename T, int BLOCK, bool LEAN>
+__device__ __forceinline__ MinMax exchange_minmax(const ResidentArgs& a, int cl, uint32_t tag, int t, int w,
+                                                  uint32_t* scratch) {
+    constexpr int W = BLOCK / kWave;
+    if (w == 0) {
+        const uint64_t deadline = wall_clock64() + a.timeout_ticks;
+        uint32_t l = 0, h = 0;
+        const bool ok = sweep_chunk(a, cl, tag, deadline, l, h, true);
+        if (lane_id() == 0) {
+            scratch[2 * W + 1] = ok ? 1u : 0u;
+            scratch[2 * W + 2] = l;
+            scratch[2 * W + 3] = h;
+        }
+    }
+    __syncthreads();
+    if (scratch[2 * W + 1] == 0u) {
+        if (t == 0) __hip_atomic_fetch_add(&a.slot->gave_up, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t l = 0xffffffffu, h = 0xffffffffu;
+        fold_missing_slices<T, BLOCK, LEAN>(a, cl, tag, l, h);
+        workgroup_umin<BLOCK>(l, h, t, w, scratch);
+        if (t == 0) {
+            scratch[2 * W + 2] = l;
+            scratch[2 * W + 3] = h;
+        }
+        __syncthreads();
+    }
+    return MinMax{from_min_space(scratch[2 * W + 2]), from_max_space(scratch[2 * W + 3])};
+}
+
+// the part of [v0, v1) that lies in the ON_CHIP vectors a slice keeps on chip: a short slice's
+// guard, compared with a lane's offset in 32 bits
+template <int ON_CHIP>
+__device__ __forceinline__ int on_chip_count(int64_t v0, int64_t v1) {
+    return (int)(v1 - v0 < (int64_t)ON_CHIP ? (v1 > v0 ? v1 - v0 : 0) : (int64_t)ON_CHIP);
+}
+
+// Rows [ROW0, ROW0 + K) of a slice from registers; `vd` is the lane's first payload byte of
+// the slice.  For a slice that holds its whole on-chip part (every slice of a bucket this
+// path takes): no per-vector guards.  FENCE4: four rows' temporaries at a time.
+template <typename T, int BLOCK, int K, int ROW0, bool FENCE4, int M>
+__device__ __forceinline__ void quant_rows(const uint4 (&r)[M], const QParams& q, uint8_t* vd) {
+    constexpr int N = Vec<T>::N;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        quant_store<T>(r[k], q, vd + (int64_t)(ROW0 + k) * BLOCK * N);
+        if (FENCE4 && k % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// the same for a short slice: only the vectors below `nloc` (on_chip_count)
+template <typename T, int BLOCK, int K, int ROW0, int M>
+__device__ __forceinline__ void quant_rows_guarded(const uint4 (&r)[M], int nloc, int t, const QParams& q,
+                                                   uint8_t* vd) {
+    constexpr int N = Vec<T>::N;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if ((ROW0 + k) * BLOCK + t < nloc) quant_store<T>(r[k], q, vd + (int64_t)(ROW0 + k) * BLOCK * N);
+}
+
+// The H parked rows, rows [ROW0, ROW0 + H) of a slice that holds its whole on-chip part, in
+// batches of SB: without per-vector guards the LDS reads of a batch issue back to back and
+// the quantise+stores pipeline (a guarded vector was its own exec-masked block that waited
+// on its own ds_read: 11 us for 36 % of the payload)
+template <typename T, int BLOCK, int H, int SB, int ROW0>
+__device__ __forceinline__ void quant_parked(const uint4* park, int t, const QParams& q, uint8_t* vd) {
+    constexpr int N = Vec<T>::N;
+#pragma unroll
+    for (int kb = 0; kb < H; kb += SB) {
+        uint4 r[SB];
+#pragma unroll
+        for (int j = 0; j < SB; ++j)
+            if (kb + j < H) r[j] = park[(kb + j) * BLOCK + t];
+#pragma unroll
+        for (int j = 0; j < SB; ++j)
+            if (kb + j < H) quant_store<T>(r[j], q, vd + (int64_t)(ROW0 + kb + j) * BLOCK * N);
+    }
+}
+
+template <typename T, int BLOCK, int H, int ROW0>
+__device__ __forceinline__ void quant_parked_guarded(const uint4* park, int nloc, int t, const QParams& q,
+                                                     uint8_t* vd) {
+    constexpr int N = Vec<T>::N;
+#pragma unroll
+    for (int k = 0; k < H; ++k)
+        if ((ROW0 + k) * BLOCK + t < nloc)
+            quant_store<T>(park[k * BLOCK + t], q, vd + (int64_t)(ROW0 + k) * BLOCK * N);
+}
+
+// the ragged top tile [top, v1) from a clamped tile (load_rows<SB>): only what is in range
+template <typename T, int BLOCK, int SB>
+__device__ __forceinline__ void quant_top_tile(const uint4 (&r)[SB], int64_t top, int64_t v1, int t,
+                                               const QParams& q, uint8_t* vdst) {
+    constexpr int N = Vec<T>::N;
+#pragma unroll
+    for (int j = 0; j < SB; ++j) {
+        const int64_t i = top + j * BLOCK + t;
+        if (i < v1) quant_store<T>(r[j], q, vdst + i * N);
+    }
+}
+
+// The nfull > 0 full streamed tiles, double-buffered from the top down (what pass 1 read
+// last of the streamed part is re-read first).  `qa` holds the top tile, requested by the
+// caller.
+template <typename T, int BLOCK, int SB, bool NT>
+__device__ __forceinline__ void quant_stream_descending(const uint4* v, int64_t stream0, int64_t nfull, int t,
+                                                        const QParams& q, uint8_t* vdst, uint4 (&qa)[SB],
+                                                        uint4 (&qb)[SB]) {
+    constexpr int N = Vec<T>::N;
+    constexpr int64_t tile = (int64_t)SB * BLOCK;
+    for (int64_t i = nfull - 1; i >= 0; i -= 2) {
+        load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 1 ? i - 1 : 0) * tile, t, qb);
+        const int64_t ba = stream0 + i * tile;
+#pragma unroll
+        for (int j = 0; j < SB; ++j) quant_store<T>(qa[j], q, vdst + (ba + j * BLOCK + t) * N);
+        load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 2 ? i - 2 : 0) * tile, t, qa);
+        if (i >= 1) {
+            const int64_t bb = ba - tile;
+#pragma unroll
+            for (int j = 0; j < SB; ++j) quant_store<T>(qb[j], q, vdst + (bb + j * BLOCK + t) * N);
+        }
+    }
+}
+
+// The same in pass 1's order: the tiles that have waited longest in the Infinity Cache are
+// re-read before the payload stores push them out.  `qa` holds tile 0.
+template <typename T, int BLOCK, int SB, bool NT>
+__device__ __forceinline__ void quant_stream_ascending(const uint4* v, int64_t stream0, int64_t nfull, int t,
+                                                       const QParams& q, uint8_t* vdst, uint4 (&qa)[SB],
+                                                       uint4 (&qb)[SB]) {
+    constexpr int N = Vec<T>::N;
+    constexpr int64_t tile = (int64_t)SB * BLOCK;
+    for (int64_t i = 0; i < nfull; i += 2) {
+        load_tile<SB, BLOCK, NT>(v, stream0 + (i + 1 < nfull ? i + 1 : nfull - 1) * tile, t, qb);
+        const int64_t ba = stream0 + i * tile;
+#pragma unroll
+        for (int j = 0; j < SB; ++j) quant_store<T>(qa[j], q, vdst + (ba + j * BLOCK + t) * N);
+        load_tile<SB, BLOCK, NT>(v, stream0 + (i + 2 < nfull ? i + 2 : nfull - 1) * tile, t, qa);
+        if (i + 1 < nfull) {
+            const int64_t bb = ba + tile;
+#pragma unroll
+            for (int j = 0; j < SB; ++j) quant_store<T>(qb[j], q, vdst + (bb + j * BLOCK + t) * N);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------
+// the kernels: one per order of the phases
+// ------------------------------------------------------------------------
+// Stream-last order.  A slice is rows [0, R) held in VGPRs, rows [R, R + H) parked in LDS,
+// the rest streamed:
+//
+//   pass 1: held, parked, streamed (ascending), a guarded ragged tail
+//   pass 2: the streamed part first, in reverse (the ragged tail, then the full tiles from
+//           the top down, the two top ones requested before the exchange), then the parked
+//           rows, then the held rows
+//
+// Every buffer is live where the source says it is: no scheduling barriers.
+// NTM: non-temporal load mask -- bit 0: pass 2's re-reads of the streamed part;
+// bit 1: pass 1's loads of the part kept on chip (held in VGPRs / parked in LDS), which
+// nothing re-reads, so they need not take Infinity-Cache lines from the streamed part
+// Trace stamps: 0 start, 1 pass 1 end, 2 exchange end, 4 streamed rows stored, 5 parked
+// rows stored, 3 end.
+template <typename T, int BLOCK, int R, int H, int SB, int NTM>
+__global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(ResidentArgs a) {
+    constexpr int N = Vec<T>::N;
+    constexpr bool NT = (NTM & 1) != 0;
+    constexpr bool NT1 = (NTM & 2) != 0;
+    // dynamic LDS only (guide Guideline 17): [H * BLOCK parked vectors][scratch]
+    extern __shared__ __attribute__((aligned(16))) uint4 smem[];
+    uint4* park = smem;
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // 2*W + 4 words
+    const int t = (int)threadIdx.x;
+    const int g = (int)blockIdx.x;
+    const int lane_c = g % kResLanes;  // the workgroup's ticket and drain counter
+
+    const uint32_t tag = draw_tag<BLOCK>(a, lane_c, t, scratch);
     trace_stamp(a, g, 0);
     if (g >= a.nact * a.bpc) {  // idle: the grid is the CU count on every launch of the slot
-        if (t == 0)
-            __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+        let_go_of_slot(a, lane_c, t);
         return;
     }
 
@@ -312,62 +627,20 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
     uint32_t hi = max_space(-T::init_max());
     uint4 held[R > 0 ? R : 1];
     if (v1 > v0) {
-        const int64_t vl = v1 - 1;  // clamp: a duplicate of a slice element never changes the min/max
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const int64_t i = v0 + (int64_t)k * BLOCK + t;
-            held[k] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-        }
-        // software-pipelined: the next batch of parked vectors is in flight while the
-        // current one (first: the held vectors) is folded, so memory never waits on VALU
-        uint4 cur[SB], nxt[SB];
-#pragma unroll
-        for (int j = 0; j < SB; ++j) {
-            if (j < H) {
-                const int64_t i = v0 + (int64_t)(R + j) * BLOCK + t;
-                cur[j] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < R; ++k) fold_vec<T>(held[k], lo, hi);
-#pragma unroll
-        for (int kb = 0; kb < H; kb += SB) {
-#pragma unroll
-            for (int j = 0; j < SB; ++j) {
-                if (kb + SB + j < H) {
-                    const int64_t i = v0 + (int64_t)(R + kb + SB + j) * BLOCK + t;
-                    nxt[j] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < SB; ++j) {
-                if (kb + j < H) {
-                    fold_vec<T>(cur[j], lo, hi);
-                    park[(kb + j) * BLOCK + t] = cur[j];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < SB; ++j) cur[j] = nxt[j];
-        }
-        // streamed part: full tiles double-buffered (2 x SB loads in flight per
-        // lane: with one wave per SIMD nothing else hides the latency), then the
-        // ragged tail tile
+        const int64_t vl = v1 - 1;
+        load_rows<R, 0, BLOCK, NT1>(v, v0, vl, t, held);
+        // the first batch of parked rows is in flight while the held rows are folded
+        uint4 cur[SB];
+        load_rows<(H < SB ? H : SB), R, BLOCK, NT1>(v, v0, vl, t, cur);
+        fold_rows<T, R, false>(held, lo, hi);
+        fold_and_park<T, BLOCK, H, SB, R, NT1>(v, v0, vl, t, cur, park, lo, hi);
+        // streamed part: the full tiles, then the ragged tail tile
         const int64_t tile = (int64_t)SB * BLOCK;
         const int64_t nfull = v1 > stream0 ? (v1 - stream0) / tile : 0;
         if (nfull > 0) {
             uint4 ra[SB], rb[SB];
             load_tile<SB, BLOCK>(v, stream0, t, ra);
-            for (int64_t i = 0; i < nfull; i += 2) {
-                // unconditional (clamped) prefetches keep the wait counts static
-                load_tile<SB, BLOCK>(v, stream0 + (i + 1 < nfull ? i + 1 : nfull - 1) * tile, t, rb);
-#pragma unroll
-                for (int j = 0; j < SB; ++j) fold_vec<T>(ra[j], lo, hi);
-                load_tile<SB, BLOCK>(v, stream0 + (i + 2 < nfull ? i + 2 : nfull - 1) * tile, t, ra);
-                if (i + 1 < nfull) {
-#pragma unroll
-                    for (int j = 0; j < SB; ++j) fold_vec<T>(rb[j], lo, hi);
-                }
-            }
+            fold_stream_ascending<T, BLOCK, SB>(v, stream0, nfull, nfull - 1, t, ra, rb, lo, hi);
         }
         for (int j = 0; j < SB; ++j) {
             const int64_t i = stream0 + nfull * tile + j * BLOCK + t;
@@ -375,18 +648,8 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
         }
     }
     if (s.last) fold_scalars<T, BLOCK>(a, s, lo, hi);
-    lo = wave_umin(lo);
-    hi = wave_umin(hi);
     const int w = t / kWave;
-    if (lane_id() == 0) { scratch[w] = lo; scratch[W + w] = hi; }
-    __syncthreads();
-    if (t == 0) {
-#pragma unroll
-        for (int i = 1; i < W; ++i) { lo = min(lo, scratch[i]); hi = min(hi, scratch[W + i]); }
-        uint64_t* mine = a.slot->gran + 2 * (int64_t)g;
-        __hip_atomic_store(mine, ((uint64_t)tag << 32) | lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 1, ((uint64_t)tag << 32) | hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    publish_partials<BLOCK>(a, g, tag, lo, hi, t, w, scratch);
 
     // the first tile pass 2 re-reads (the top full tile: reverse order) is loaded
     // now, so its latency overlaps the exchange wait instead of following it
@@ -397,41 +660,12 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
     if (nfull2 > 1) load_tile<SB, BLOCK, NT>(v, stream0 + (nfull2 - 2) * tile2, t, pre2);
 
     trace_stamp(a, g, 1);
-    // ---- exchange ------------------------------------------------------------
-    if (w == 0) {
-        const uint64_t deadline = wall_clock64() + a.timeout_ticks;
-        uint32_t l = 0, h = 0;
-        const bool ok = sweep_chunk(a, s.cl, tag, deadline, l, h, true);
-        if (lane_id() == 0) {
-            scratch[2 * W + 1] = ok ? 1u : 0u;
-            scratch[2 * W + 2] = l;
-            scratch[2 * W + 3] = h;
-        }
-    }
-    __syncthreads();
-    if (scratch[2 * W + 1] == 0u) {
-        // gave up waiting: the whole workgroup folds the missing slices itself
-        if (t == 0) __hip_atomic_fetch_add(&a.slot->gave_up, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t l = 0xffffffffu, h = 0xffffffffu;
-        fold_missing_slices<T, BLOCK>(a, s.cl, tag, l, h);
-        l = wave_umin(l);
-        h = wave_umin(h);
-        if (lane_id() == 0) { scratch[w] = l; scratch[W + w] = h; }
-        __syncthreads();
-        if (t == 0) {
-#pragma unroll
-            for (int i = 1; i < W; ++i) { l = min(l, scratch[i]); h = min(h, scratch[W + i]); }
-            scratch[2 * W + 2] = l;
-            scratch[2 * W + 3] = h;
-        }
-        __syncthreads();
-    }
-    const float mn = from_min_space(scratch[2 * W + 2]), mx = from_max_space(scratch[2 * W + 3]);
-    const QParams q = make_qparams(mn, mx);
+    const MinMax m = exchange_minmax<T, BLOCK, false>(a, s.cl, tag, t, w, scratch);
+    const QParams q = make_qparams(m.mn, m.mx);
     trace_stamp(a, g, 2);
 
     // ---- pass 2 ------------------------------------------------------------
-    write_extras<T, BLOCK>(a, s, mn, mx, q);
+    write_extras<T, BLOCK>(a, s, m.mn, m.mx, q);
     uint8_t* vdst = s.payload + s.j0;
     if (v1 > stream0) {
         // reverse order (what pass 1 read last is re-read first): the ragged
@@ -443,6 +677,7 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
             if (i < v1) quant_store<T>(v[i], q, vdst + i * N);
         }
         if (nfull > 0) {
+            // as quant_stream_descending, but the first two tiles are already here
             uint4 ra[SB], rb[SB];
 #pragma unroll
             for (int j = 0; j < SB; ++j) { ra[j] = pre[j]; rb[j] = pre2[j]; }  // loaded before the exchange
@@ -462,25 +697,12 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
     }
     trace_stamp(a, g, 4);
     if (v0 + (int64_t)(R + H) * BLOCK <= v1) {
-        // the whole on-chip part is inside the slice (every slice of a bucket this path
-        // takes): no per-vector guards, so the LDS reads of a batch issue back to back
-        // and the quantise+stores pipeline (a guarded vector was its own exec-masked
-        // block that waited on its own ds_read: 11 us for 36 % of the payload)
         uint8_t* vd = vdst + (v0 + t) * N;
-#pragma unroll
-        for (int kb = 0; kb < H; kb += SB) {
-            uint4 r[SB];
-#pragma unroll
-            for (int j = 0; j < SB; ++j)
-                if (kb + j < H) r[j] = park[(kb + j) * BLOCK + t];
-#pragma unroll
-            for (int j = 0; j < SB; ++j)
-                if (kb + j < H) quant_store<T>(r[j], q, vd + (int64_t)(R + kb + j) * BLOCK * N);
-        }
+        quant_parked<T, BLOCK, H, SB, R>(park, t, q, vd);
         trace_stamp(a, g, 5);
-#pragma unroll
-        for (int k = 0; k < R; ++k) quant_store<T>(held[k], q, vd + (int64_t)k * BLOCK * N);
+        quant_rows<T, BLOCK, R, 0, false>(held, q, vd);
     } else {
+        // a short slice, guarded per vector against v1 itself
 #pragma unroll
         for (int k = 0; k < H; ++k) {
             const int64_t i = v0 + (int64_t)(R + k) * BLOCK + t;
@@ -493,35 +715,11 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
             if (i < v1) quant_store<T>(held[k], q, vdst + i * N);
         }
     }
-    if (a.trace != nullptr) {
-        __syncthreads();
-        trace_stamp(a, g, 3);
-    }
-    // the workgroup let go of the slot (its granule reads ended at the exchange's
-    // barriers); counted last, so no later load waits behind this atomic (on gfx9
-    // a non-returning atomic still holds vmcnt: mid-kernel it cost ~1.3 us,
-    // profiles/r03_resident_versions_ab.jsonl)
-    if (t == 0)
-        __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    finish(a, g, lane_c, t);
 }
 
-// One tile of SB rows whose vector indices are clamped to `vl` (the slice's last
-// vector): a ragged tile loads like a full one, all SB loads in flight together;
-// the duplicates never change a min/max, and pass 2 stores only what is in range.
-template <int SB, int BLOCK, bool NT>
-__device__ __forceinline__ void load_tile_clamped(const uint4* __restrict__ v, int64_t base, int64_t vl, int t,
-                                                  uint4 (&r)[SB]) {
-#pragma unroll
-    for (int j = 0; j < SB; ++j) {
-        const int64_t i = base + j * BLOCK + t;
-        r[j] = NT ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-    }
-}
-
-// Stack order: the same slice layout as minmax_resident_encode_kernel (rows [0, R)
-// of a slice held in VGPRs, rows [R, R + H) parked in LDS, the rest streamed; a row
-// is BLOCK vectors), with the passes turned round so that the held rows are never
-// live together with the streaming buffers:
+// Stack order: the same slice layout as minmax_resident_encode_kernel, with the passes
+// turned round so that the held rows are never live together with the streaming buffers:
 //
 //   pass 1: the streamed rows first (ascending, double-buffered), then the parked
 //           rows, then the held rows, loaded last into the registers the streaming
@@ -532,11 +730,10 @@ __device__ __forceinline__ void load_tile_clamped(const uint4* __restrict__ v, i
 //           runs under the parked rows' quantisation.
 //
 // The register budget is max(4R, streaming buffers) + temporaries instead of their
-// sum, which is what lets R grow past 28 at BLOCK = 512 without scratch.  Slice
-// ownership, scalars, header and slack, the exchange, the give-up path, tickets
-// and the drain counter are those of minmax_resident_encode_kernel.
+// sum, which is what lets R grow past 28 at BLOCK = 512 without scratch.
 // EARLY: the first streamed tile is requested before the ticket is drawn (the tag
 // is only needed when the partials are published).
+// ASC: pass 2 re-reads the full streamed tiles in pass 1's order.
 // Trace stamps: 0 start, 1 pass 1 end, 2 exchange end, 6 held rows stored,
 // 7 parked rows stored, 3 end.
 template <typename T, int BLOCK, int R, int H, int SB, int NTM, bool EARLY, bool ASC>
@@ -544,14 +741,13 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
     constexpr int N = Vec<T>::N;
     constexpr bool NT = (NTM & 1) != 0;
     constexpr bool NT1 = (NTM & 2) != 0;
-    constexpr int W = BLOCK / kWave;
     static_assert(R > 0 && H > 0, "the stack order keeps rows in VGPRs and in LDS");
     extern __shared__ __attribute__((aligned(16))) uint4 smem[];
     uint4* park = smem;
     uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // 2*W + 4 words
     const int t = (int)threadIdx.x;
     const int g = (int)blockIdx.x;
-    const int lane_c = g % kResLanes;
+    const int lane_c = g % kResLanes;  // the workgroup's ticket and drain counter
     const bool idle = g >= a.nact * a.bpc;  // the grid is the CU count on every launch of the slot
 
     const SliceGeom<T, BLOCK> s(a, idle ? 0 : g);
@@ -565,18 +761,10 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
 
     uint4 ra[SB];
     if (EARLY && !idle && nfull > 0) load_tile<SB, BLOCK>(v, stream0, t, ra);
-    if (t == 0) {
-        const uint64_t ticket = __hip_atomic_fetch_add(&a.slot->ticket[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
-        scratch[2 * W] = tag_of_ticket(ticket, a.grid, lane_c);
-    }
-    __syncthreads();
-    const uint32_t tag = scratch[2 * W];
+    const uint32_t tag = draw_tag<BLOCK>(a, lane_c, t, scratch);
     trace_stamp(a, g, 0);
     if (idle) {
-        if (t == 0)
-            __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+        let_go_of_slot(a, lane_c, t);
         return;
     }
 
@@ -588,83 +776,34 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
         uint4 rb[SB];
         if (nfull > 0) {
             if (!EARLY) load_tile<SB, BLOCK>(v, stream0, t, ra);
-            for (int64_t i = 0; i < nfull; i += 2) {
-                // unconditional (clamped) prefetches keep the wait counts static
-                load_tile<SB, BLOCK>(v, stream0 + (i + 1 < nfull ? i + 1 : nfull - 1) * tile, t, rb);
-#pragma unroll
-                for (int j = 0; j < SB; ++j) fold_vec<T>(ra[j], lo, hi);
-                load_tile<SB, BLOCK>(v, stream0 + (i + 2 < nfull ? i + 2 : nfull - 1) * tile, t, ra);
-                if (i + 1 < nfull) {
-#pragma unroll
-                    for (int j = 0; j < SB; ++j) fold_vec<T>(rb[j], lo, hi);
-                }
-            }
+            fold_stream_ascending<T, BLOCK, SB>(v, stream0, nfull, nfull - 1, t, ra, rb, lo, hi);
         }
         // the ragged top tile and the first batch of parked rows are requested together
-        uint4 cur[SB], nxt[SB];
-        if (v1 > top) load_tile_clamped<SB, BLOCK, false>(v, top, vl, t, rb);
-#pragma unroll
-        for (int j = 0; j < SB; ++j) {
-            if (j < H) {
-                const int64_t i = v0 + (int64_t)(R + j) * BLOCK + t;
-                cur[j] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-            }
-        }
-        if (v1 > top) {
-#pragma unroll
-            for (int j = 0; j < SB; ++j) fold_vec<T>(rb[j], lo, hi);
-        }
-#pragma unroll
-        for (int kb = 0; kb < H; kb += SB) {
-#pragma unroll
-            for (int j = 0; j < SB; ++j) {
-                if (kb + SB + j < H) {
-                    const int64_t i = v0 + (int64_t)(R + kb + SB + j) * BLOCK + t;
-                    nxt[j] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < SB; ++j) {
-                if (kb + j < H) {
-                    fold_vec<T>(cur[j], lo, hi);
-                    park[(kb + j) * BLOCK + t] = cur[j];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < SB; ++j) cur[j] = nxt[j];
-        }
+        uint4 cur[SB];
+        if (v1 > top) load_rows<SB, 0, BLOCK, false>(v, top, vl, t, rb);
+        load_rows<(H < SB ? H : SB), R, BLOCK, NT1>(v, v0, vl, t, cur);
+        if (v1 > top) fold_rows<T, SB, false>(rb, lo, hi);
+        fold_and_park<T, BLOCK, H, SB, R, NT1>(v, v0, vl, t, cur, park, lo, hi);
         // the held rows, last: every streaming buffer above is dead.  The scheduling
         // barriers keep it so: without them the scheduler lifts these loads over the
         // parked rows and expands every row's keys at once, which spills.
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const int64_t i = v0 + (int64_t)k * BLOCK + t;
-            held[k] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-        }
+        load_rows<R, 0, BLOCK, NT1>(v, v0, vl, t, held);
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            fold_vec<T>(held[k], lo, hi);
-            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);
-        }
+        fold_rows<T, R, true>(held, lo, hi);
     }
     if (s.last) fold_scalars<T, BLOCK>(a, s, lo, hi);
-    lo = wave_umin(lo);
-    hi = wave_umin(hi);
     const int w = t / kWave;
-    if (lane_id() == 0) { scratch[w] = lo; scratch[W + w] = hi; }
-    __syncthreads();
-    if (t == 0) {
-#pragma unroll
-        for (int i = 1; i < W; ++i) { lo = min(lo, scratch[i]); hi = min(hi, scratch[W + i]); }
-        uint64_t* mine = a.slot->gran + 2 * (int64_t)g;
-        __hip_atomic_store(mine, ((uint64_t)tag << 32) | lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 1, ((uint64_t)tag << 32) | hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    publish_partials<BLOCK>(a, g, tag, lo, hi, t, w, scratch);
     trace_stamp(a, g, 1);
 
-    // ---- exchange ------------------------------------------------------------
+    // The exchange, written out: exchange_minmax<T, BLOCK, true> is this text, but called as a
+    // helper it costs this kernel two more SGPRs across the give-up path, and the f32 rows with
+    // R = 52 (17, 19, 24, 25), which sit at 256 VGPRs, then spill them to scratch
+    // (test_default_rows_use_no_scratch checks row 24).  A change to one is a change to both:
+    // tests/test_resident_source.py compares the text between the two marks with the helper's.
+    constexpr int W = BLOCK / kWave;
+    // exchange_minmax: begin
     if (w == 0) {
         const uint64_t deadline = wall_clock64() + a.timeout_ticks;
         uint32_t l = 0, h = 0;
@@ -677,115 +816,44 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
     }
     __syncthreads();
     if (scratch[2 * W + 1] == 0u) {
-        // gave up waiting: the whole workgroup folds the missing slices itself
         if (t == 0) __hip_atomic_fetch_add(&a.slot->gave_up, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         uint32_t l = 0xffffffffu, h = 0xffffffffu;
         fold_missing_slices<T, BLOCK, true>(a, s.cl, tag, l, h);
-        l = wave_umin(l);
-        h = wave_umin(h);
-        if (lane_id() == 0) { scratch[w] = l; scratch[W + w] = h; }
-        __syncthreads();
+        workgroup_umin<BLOCK>(l, h, t, w, scratch);
         if (t == 0) {
-#pragma unroll
-            for (int i = 1; i < W; ++i) { l = min(l, scratch[i]); h = min(h, scratch[W + i]); }
             scratch[2 * W + 2] = l;
             scratch[2 * W + 3] = h;
         }
         __syncthreads();
     }
-    const float mn = from_min_space(scratch[2 * W + 2]), mx = from_max_space(scratch[2 * W + 3]);
-    const QParams q = make_qparams(mn, mx);
+    const MinMax m{from_min_space(scratch[2 * W + 2]), from_max_space(scratch[2 * W + 3])};
+    // exchange_minmax: end
+    const QParams q = make_qparams(m.mn, m.mx);
     trace_stamp(a, g, 2);
 
     // ---- pass 2 ------------------------------------------------------------
-    write_extras<T, BLOCK>(a, s, mn, mx, q);
+    write_extras<T, BLOCK>(a, s, m.mn, m.mx, q);
     uint8_t* vdst = s.payload + s.j0;
     const bool whole = stream0 <= v1;  // the whole on-chip part is inside the slice: no per-vector guards
     uint8_t* vd = vdst + (v0 + t) * N;
-    // a short slice's guard: its vector count against the lane's offset, in 32 bits
-    const int nloc = (int)(v1 - v0 < (int64_t)(R + H) * BLOCK ? (v1 > v0 ? v1 - v0 : 0) : (int64_t)(R + H) * BLOCK);
-    if (whole) {
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            quant_store<T>(held[k], q, vd + (int64_t)k * BLOCK * N);
-            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // four rows' temporaries at a time
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < R; ++k)
-            if (k * BLOCK + t < nloc) quant_store<T>(held[k], q, vd + (int64_t)k * BLOCK * N);
-    }
+    const int nloc = on_chip_count<(R + H) * BLOCK>(v0, v1);
+    if (whole) quant_rows<T, BLOCK, R, 0, true>(held, q, vd);
+    else quant_rows_guarded<T, BLOCK, R, 0>(held, nloc, t, q, vd);
     __builtin_amdgcn_sched_barrier(0);  // no streamed tile is requested while held rows are live
     trace_stamp(a, g, 6);
     // the two top streamed tiles (the ragged one, then the top full one), in flight
     // while the parked rows are quantised
     // (buffers of their own: pass 1's would count as live across the exchange)
     uint4 qa[SB], qb[SB];
-    if (v1 > top) load_tile_clamped<SB, BLOCK, NT>(v, top, vl, t, qb);
+    if (v1 > top) load_rows<SB, 0, BLOCK, NT>(v, top, vl, t, qb);
     if (nfull > 0) load_tile<SB, BLOCK, NT>(v, stream0 + (ASC ? 0 : nfull - 1) * tile, t, qa);
-    if (whole) {
-#pragma unroll
-        for (int kb = 0; kb < H; kb += SB) {
-            uint4 r[SB];
-#pragma unroll
-            for (int j = 0; j < SB; ++j)
-                if (kb + j < H) r[j] = park[(kb + j) * BLOCK + t];
-#pragma unroll
-            for (int j = 0; j < SB; ++j)
-                if (kb + j < H) quant_store<T>(r[j], q, vd + (int64_t)(R + kb + j) * BLOCK * N);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < H; ++k)
-            if ((R + k) * BLOCK + t < nloc)
-                quant_store<T>(park[k * BLOCK + t], q, vd + (int64_t)(R + k) * BLOCK * N);
-    }
+    if (whole) quant_parked<T, BLOCK, H, SB, R>(park, t, q, vd);
+    else quant_parked_guarded<T, BLOCK, H, R>(park, nloc, t, q, vd);
     trace_stamp(a, g, 7);
-    if (v1 > top) {
-#pragma unroll
-        for (int j = 0; j < SB; ++j) {
-            const int64_t i = top + j * BLOCK + t;
-            if (i < v1) quant_store<T>(qb[j], q, vdst + i * N);
-        }
-    }
-    if (ASC && nfull > 0) {
-        // full tiles double-buffered in pass 1's order: the tiles that have waited longest
-        // in the Infinity Cache are re-read before the payload stores push them out
-        for (int64_t i = 0; i < nfull; i += 2) {
-            load_tile<SB, BLOCK, NT>(v, stream0 + (i + 1 < nfull ? i + 1 : nfull - 1) * tile, t, qb);
-            const int64_t ba = stream0 + i * tile;
-#pragma unroll
-            for (int j = 0; j < SB; ++j) quant_store<T>(qa[j], q, vdst + (ba + j * BLOCK + t) * N);
-            load_tile<SB, BLOCK, NT>(v, stream0 + (i + 2 < nfull ? i + 2 : nfull - 1) * tile, t, qa);
-            if (i + 1 < nfull) {
-                const int64_t bb = ba + tile;
-#pragma unroll
-                for (int j = 0; j < SB; ++j) quant_store<T>(qb[j], q, vdst + (bb + j * BLOCK + t) * N);
-            }
-        }
-    } else if (nfull > 0) {
-        // full tiles double-buffered from the top down (what pass 1 read last of the
-        // streamed part is re-read first)
-        for (int64_t i = nfull - 1; i >= 0; i -= 2) {
-            load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 1 ? i - 1 : 0) * tile, t, qb);
-            const int64_t ba = stream0 + i * tile;
-#pragma unroll
-            for (int j = 0; j < SB; ++j) quant_store<T>(qa[j], q, vdst + (ba + j * BLOCK + t) * N);
-            load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 2 ? i - 2 : 0) * tile, t, qa);
-            if (i >= 1) {
-                const int64_t bb = ba - tile;
-#pragma unroll
-                for (int j = 0; j < SB; ++j) quant_store<T>(qb[j], q, vdst + (bb + j * BLOCK + t) * N);
-            }
-        }
-    }
-    if (a.trace != nullptr) {
-        __syncthreads();
-        trace_stamp(a, g, 3);
-    }
-    // counted last, as in minmax_resident_encode_kernel
-    if (t == 0)
-        __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (v1 > top) quant_top_tile<T, BLOCK, SB>(qb, top, v1, t, q, vdst);
+    if (ASC && nfull > 0) quant_stream_ascending<T, BLOCK, SB, NT>(v, stream0, nfull, t, q, vdst, qa, qb);
+    else if (nfull > 0) quant_stream_descending<T, BLOCK, SB, NT>(v, stream0, nfull, t, q, vdst, qa, qb);
+    finish(a, g, lane_c, t);
 }
 
 // Window order: the stream-last order of minmax_resident_encode_kernel, with the stack
@@ -803,9 +871,7 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
 // Between a streamed row's read and its re-read only the late rows' loads and stores go
 // by (the stack order puts the whole on-chip part there), so the re-read finds more of
 // its lines in the Infinity Cache; the register budget is
-// 4 RE + max(streaming buffers, 4 RL) + temporaries.  Slice ownership, scalars, header
-// and slack, the exchange, the give-up path, tickets and the drain counter are those of
-// minmax_resident_encode_kernel.
+// 4 RE + max(streaming buffers, 4 RL) + temporaries.
 // Trace stamps: 0 start, 1 pass 1 end, 2 exchange end, 6 late rows stored, 4 streamed
 // rows stored, 5 parked rows stored, 3 end.
 template <typename T, int BLOCK, int RE, int H, int RL, int SB, int NTM>
@@ -813,27 +879,18 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_window
     constexpr int N = Vec<T>::N;
     constexpr bool NT = (NTM & 1) != 0;
     constexpr bool NT1 = (NTM & 2) != 0;
-    constexpr int W = BLOCK / kWave;
     static_assert(RE > 0 && H > 0 && RL > 0, "the window order keeps rows in VGPRs (early and late) and in LDS");
     extern __shared__ __attribute__((aligned(16))) uint4 smem[];
     uint4* park = smem;
     uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // 2*W + 4 words
     const int t = (int)threadIdx.x;
     const int g = (int)blockIdx.x;
+    const int lane_c = g % kResLanes;  // the workgroup's ticket and drain counter
 
-    const int lane_c = g % kResLanes;
-    if (t == 0) {
-        const uint64_t ticket = __hip_atomic_fetch_add(&a.slot->ticket[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
-        scratch[2 * W] = tag_of_ticket(ticket, a.grid, lane_c);
-    }
-    __syncthreads();
-    const uint32_t tag = scratch[2 * W];
+    const uint32_t tag = draw_tag<BLOCK>(a, lane_c, t, scratch);
     trace_stamp(a, g, 0);
     if (g >= a.nact * a.bpc) {  // idle: the grid is the CU count on every launch of the slot
-        if (t == 0)
-            __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+        let_go_of_slot(a, lane_c, t);
         return;
     }
 
@@ -851,215 +908,69 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_window
     uint32_t hi = max_space(-T::init_max());
     uint4 held[RE], late[RL];
     if (v1 > v0) {
-#pragma unroll
-        for (int k = 0; k < RE; ++k) {
-            const int64_t i = v0 + (int64_t)k * BLOCK + t;
-            held[k] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-        }
-        // software-pipelined as in minmax_resident_encode_kernel: the next batch of parked
-        // rows is in flight while the current one (first: the early rows) is folded
-        uint4 cur[SB], nxt[SB];
-#pragma unroll
-        for (int j = 0; j < SB; ++j) {
-            if (j < H) {
-                const int64_t i = v0 + (int64_t)(RE + j) * BLOCK + t;
-                cur[j] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < RE; ++k) {
-            fold_vec<T>(held[k], lo, hi);
-            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // four rows' keys at a time
-        }
-#pragma unroll
-        for (int kb = 0; kb < H; kb += SB) {
-#pragma unroll
-            for (int j = 0; j < SB; ++j) {
-                if (kb + SB + j < H) {
-                    const int64_t i = v0 + (int64_t)(RE + kb + SB + j) * BLOCK + t;
-                    nxt[j] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < SB; ++j) {
-                if (kb + j < H) {
-                    fold_vec<T>(cur[j], lo, hi);
-                    park[(kb + j) * BLOCK + t] = cur[j];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < SB; ++j) cur[j] = nxt[j];
-        }
-        // streamed rows: full tiles double-buffered, then the ragged top tile (clamped)
+        load_rows<RE, 0, BLOCK, NT1>(v, v0, vl, t, held);
+        // the first batch of parked rows is in flight while the early rows are folded
+        uint4 cur[SB];
+        load_rows<(H < SB ? H : SB), RE, BLOCK, NT1>(v, v0, vl, t, cur);
+        fold_rows<T, RE, true>(held, lo, hi);
+        fold_and_park<T, BLOCK, H, SB, RE, NT1>(v, v0, vl, t, cur, park, lo, hi);
+        // streamed rows: the full tiles, then the ragged top tile (clamped)
         uint4 ra[SB], rb[SB];
         if (nfull > 0) {
             load_tile<SB, BLOCK>(v, stream0, t, ra);
-            for (int64_t i = 0; i < nfull; i += 2) {
-                // unconditional (clamped) prefetches keep the wait counts static
-                load_tile<SB, BLOCK>(v, stream0 + (i + 1 < nfull ? i + 1 : nfull - 1) * tile, t, rb);
-#pragma unroll
-                for (int j = 0; j < SB; ++j) fold_vec<T>(ra[j], lo, hi);
-                load_tile<SB, BLOCK>(v, stream0 + (i + 2 < nfull ? i + 2 : nfull - 1) * tile, t, ra);
-                if (i + 1 < nfull) {
-#pragma unroll
-                    for (int j = 0; j < SB; ++j) fold_vec<T>(rb[j], lo, hi);
-                }
-            }
+            fold_stream_ascending<T, BLOCK, SB>(v, stream0, nfull, nfull - 1, t, ra, rb, lo, hi);
         }
         if (v1 > top) {
-            load_tile_clamped<SB, BLOCK, false>(v, top, vl, t, rb);
-#pragma unroll
-            for (int j = 0; j < SB; ++j) fold_vec<T>(rb[j], lo, hi);
+            load_rows<SB, 0, BLOCK, false>(v, top, vl, t, rb);
+            fold_rows<T, SB, false>(rb, lo, hi);
         }
         // the late rows, last: every streaming buffer above is dead.  The scheduling
         // barriers keep it so (see minmax_resident_encode_kernel_stack).
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < RL; ++k) {
-            const int64_t i = v0 + (int64_t)(RE + H + k) * BLOCK + t;
-            late[k] = NT1 ? nt_load16(&v[i < vl ? i : vl]) : v[i < vl ? i : vl];
-        }
+        load_rows<RL, RE + H, BLOCK, NT1>(v, v0, vl, t, late);
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < RL; ++k) {
-            fold_vec<T>(late[k], lo, hi);
-            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);
-        }
+        fold_rows<T, RL, true>(late, lo, hi);
     }
     if (s.last) fold_scalars<T, BLOCK>(a, s, lo, hi);
-    lo = wave_umin(lo);
-    hi = wave_umin(hi);
     const int w = t / kWave;
-    if (lane_id() == 0) { scratch[w] = lo; scratch[W + w] = hi; }
-    __syncthreads();
-    if (t == 0) {
-#pragma unroll
-        for (int i = 1; i < W; ++i) { lo = min(lo, scratch[i]); hi = min(hi, scratch[W + i]); }
-        uint64_t* mine = a.slot->gran + 2 * (int64_t)g;
-        __hip_atomic_store(mine, ((uint64_t)tag << 32) | lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 1, ((uint64_t)tag << 32) | hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    publish_partials<BLOCK>(a, g, tag, lo, hi, t, w, scratch);
     trace_stamp(a, g, 1);
 
-    // ---- exchange ------------------------------------------------------------
-    if (w == 0) {
-        const uint64_t deadline = wall_clock64() + a.timeout_ticks;
-        uint32_t l = 0, h = 0;
-        const bool ok = sweep_chunk(a, s.cl, tag, deadline, l, h, true);
-        if (lane_id() == 0) {
-            scratch[2 * W + 1] = ok ? 1u : 0u;
-            scratch[2 * W + 2] = l;
-            scratch[2 * W + 3] = h;
-        }
-    }
-    __syncthreads();
-    if (scratch[2 * W + 1] == 0u) {
-        // gave up waiting: the whole workgroup folds the missing slices itself
-        if (t == 0) __hip_atomic_fetch_add(&a.slot->gave_up, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t l = 0xffffffffu, h = 0xffffffffu;
-        fold_missing_slices<T, BLOCK, true>(a, s.cl, tag, l, h);
-        l = wave_umin(l);
-        h = wave_umin(h);
-        if (lane_id() == 0) { scratch[w] = l; scratch[W + w] = h; }
-        __syncthreads();
-        if (t == 0) {
-#pragma unroll
-            for (int i = 1; i < W; ++i) { l = min(l, scratch[i]); h = min(h, scratch[W + i]); }
-            scratch[2 * W + 2] = l;
-            scratch[2 * W + 3] = h;
-        }
-        __syncthreads();
-    }
-    const float mn = from_min_space(scratch[2 * W + 2]), mx = from_max_space(scratch[2 * W + 3]);
-    const QParams q = make_qparams(mn, mx);
+    const MinMax m = exchange_minmax<T, BLOCK, true>(a, s.cl, tag, t, w, scratch);
+    const QParams q = make_qparams(m.mn, m.mx);
     trace_stamp(a, g, 2);
 
     // ---- pass 2 ------------------------------------------------------------
-    write_extras<T, BLOCK>(a, s, mn, mx, q);
+    write_extras<T, BLOCK>(a, s, m.mn, m.mx, q);
     uint8_t* vdst = s.payload + s.j0;
     const bool whole = stream0 <= v1;  // the whole on-chip part is inside the slice: no per-vector guards
     uint8_t* vd = vdst + (v0 + t) * N;
-    // a short slice's guard: its vector count against the lane's offset, in 32 bits
-    constexpr int kOnChip = (RE + H + RL) * BLOCK;
-    const int nloc = (int)(v1 - v0 < (int64_t)kOnChip ? (v1 > v0 ? v1 - v0 : 0) : (int64_t)kOnChip);
-    if (whole) {
-#pragma unroll
-        for (int k = 0; k < RL; ++k) {
-            quant_store<T>(late[k], q, vd + (int64_t)(RE + H + k) * BLOCK * N);
-            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);  // four rows' temporaries at a time
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < RL; ++k)
-            if ((RE + H + k) * BLOCK + t < nloc) quant_store<T>(late[k], q, vd + (int64_t)(RE + H + k) * BLOCK * N);
-    }
+    const int nloc = on_chip_count<(RE + H + RL) * BLOCK>(v0, v1);
+    if (whole) quant_rows<T, BLOCK, RL, RE + H, true>(late, q, vd);
+    else quant_rows_guarded<T, BLOCK, RL, RE + H>(late, nloc, t, q, vd);
     __builtin_amdgcn_sched_barrier(0);  // no streamed tile is requested while late rows are live
     trace_stamp(a, g, 6);
     // the two top streamed tiles (the ragged one, then the top full one) are requested now
     // (buffers of their own: pass 1's would count as live across the exchange)
     {
         uint4 qa[SB], qb[SB];
-        if (v1 > top) load_tile_clamped<SB, BLOCK, NT>(v, top, vl, t, qb);
+        if (v1 > top) load_rows<SB, 0, BLOCK, NT>(v, top, vl, t, qb);
         if (nfull > 0) load_tile<SB, BLOCK, NT>(v, stream0 + (nfull - 1) * tile, t, qa);
-        if (v1 > top) {
-#pragma unroll
-            for (int j = 0; j < SB; ++j) {
-                const int64_t i = top + j * BLOCK + t;
-                if (i < v1) quant_store<T>(qb[j], q, vdst + i * N);
-            }
-        }
-        if (nfull > 0) {
-            // full tiles double-buffered from the top down (what pass 1 read last of the
-            // streamed part is re-read first)
-            for (int64_t i = nfull - 1; i >= 0; i -= 2) {
-                load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 1 ? i - 1 : 0) * tile, t, qb);
-                const int64_t ba = stream0 + i * tile;
-#pragma unroll
-                for (int j = 0; j < SB; ++j) quant_store<T>(qa[j], q, vdst + (ba + j * BLOCK + t) * N);
-                load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 2 ? i - 2 : 0) * tile, t, qa);
-                if (i >= 1) {
-                    const int64_t bb = ba - tile;
-#pragma unroll
-                    for (int j = 0; j < SB; ++j) quant_store<T>(qb[j], q, vdst + (bb + j * BLOCK + t) * N);
-                }
-            }
-        }
+        if (v1 > top) quant_top_tile<T, BLOCK, SB>(qb, top, v1, t, q, vdst);
+        if (nfull > 0) quant_stream_descending<T, BLOCK, SB, NT>(v, stream0, nfull, t, q, vdst, qa, qb);
     }
     __builtin_amdgcn_sched_barrier(0);
     trace_stamp(a, g, 4);
     if (whole) {
-#pragma unroll
-        for (int kb = 0; kb < H; kb += SB) {
-            uint4 r[SB];
-#pragma unroll
-            for (int j = 0; j < SB; ++j)
-                if (kb + j < H) r[j] = park[(kb + j) * BLOCK + t];
-#pragma unroll
-            for (int j = 0; j < SB; ++j)
-                if (kb + j < H) quant_store<T>(r[j], q, vd + (int64_t)(RE + kb + j) * BLOCK * N);
-        }
+        quant_parked<T, BLOCK, H, SB, RE>(park, t, q, vd);
         trace_stamp(a, g, 5);
-#pragma unroll
-        for (int k = 0; k < RE; ++k) {
-            quant_store<T>(held[k], q, vd + (int64_t)k * BLOCK * N);
-            if (k % 4 == 3) __builtin_amdgcn_sched_barrier(0);
-        }
+        quant_rows<T, BLOCK, RE, 0, true>(held, q, vd);
     } else {
-#pragma unroll
-        for (int k = 0; k < H; ++k)
-            if ((RE + k) * BLOCK + t < nloc) quant_store<T>(park[k * BLOCK + t], q, vd + (int64_t)(RE + k) * BLOCK * N);
+        quant_parked_guarded<T, BLOCK, H, RE>(park, nloc, t, q, vd);
         trace_stamp(a, g, 5);
-#pragma unroll
-        for (int k = 0; k < RE; ++k)
-            if (k * BLOCK + t < nloc) quant_store<T>(held[k], q, vd + (int64_t)k * BLOCK * N);
+        quant_rows_guarded<T, BLOCK, RE, 0>(held, nloc, t, q, vd);
     }
-    if (a.trace != nullptr) {
-        __syncthreads();
-        trace_stamp(a, g, 3);
-    }
-    // counted last, as in minmax_resident_encode_kernel
-    if (t == 0)
-        __hip_atomic_fetch_add(&a.slot->drained[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    finish(a, g, lane_c, t);
 }
 
 // ------------------------------------------------------------------------
@@ -1135,7 +1046,13 @@ static constexpr ResidentCfg kResCfg[] = {
     {512, 28, 19, 8, 0},   // 9
     {256, 80, 39, 8, 1},    // 10
     {512, 28, 19, 8, 1},       // 11
-    {512, 28, 19, 8, 3},       // 12: 11 + the on-chip part loaded non-temporally
+    // 12: 11 with the on-chip part of pass 1 also loaded non-temporally (the default before the
+    // stack and window orders).  The one-bucket loop is unchanged (1,894-1,898 vs 1,892-1,916
+    // GiB/s), and alternating buckets -- a bucket last touched a whole other bucket ago, as in
+    // training -- gain 1,900-1,928 vs 1,849-1,886 GiB/s (profiles/r04_resident_ntm_ab.jsonl; 13,
+    // the on-chip part non-temporal with default re-reads, shortens the encode to 78-80 us but
+    // slows the decode after it by as much)
+    {512, 28, 19, 8, 3},       // 12
     {512, 28, 19, 8, 2},       // 13: only the on-chip part non-temporal
     // stack-order passes (minmax_resident_encode_kernel_stack): held rows and streaming
     // buffers share registers, so R grows without scratch; non-temporal as in 12
@@ -1163,24 +1080,15 @@ static constexpr ResidentCfg kResCfg[] = {
 };
 constexpr int kResNumCfg = (int)(sizeof(kResCfg) / sizeof(kResCfg[0]));
 static_assert(kResCfg[29].rl == 0 && kResCfg[31].rl == 8 && kResCfg[32].rl == 12, "row numbers are named by BAGUA_RESIDENT_CFG and the tests");
-// 12: config 11 with the on-chip part of pass 1 also loaded non-temporally.  The
-// one-bucket loop is unchanged (1,894-1,898 vs 1,892-1,916 GiB/s), and alternating
-// buckets -- a bucket last touched a whole other bucket ago, as in training -- gain
-// 1,900-1,928 vs 1,849-1,886 GiB/s (profiles/r04_resident_ntm_ab.jsonl; 13, the
-// on-chip part non-temporal with default re-reads, shortens the encode to 78-80 us
-// but slows the decode after it by as much)
-constexpr int kResDefaultCfg = 12;
-// Per dtype, from the stack-order and window-order sweeps (profiles/resident_stack_ab.jsonl,
-// profiles/resident_window_*.json*): f32 takes 32 (window order, 40 rows held
-// early + 12 late: 55 % of the bucket on chip as in 24, 256 VGPRs, no scratch, and a fresher
-// re-read), bf16 takes 31 (44 + 8, likewise) and f16 stays on 29 (stack order, R = 44: the f16
-// kernels need more temporaries; its only window row without scratch, 36 + 8, lost to 29).
-// No default may use scratch (bagua_minmax_u8_resident_cfg_info,
+// The default row per dtype, from the stack-order and window-order sweeps
+// (profiles/resident_stack_ab.jsonl, profiles/resident_window_*.json*): f32 takes 32
+// (window order, 40 rows held early + 12 late: 55 % of the bucket on chip as in 24, 256 VGPRs, no
+// scratch, and a fresher re-read), bf16 takes 31 (44 + 8, likewise) and f16 stays on 29 (stack
+// order, R = 44: the f16 kernels need more temporaries; its only window row without scratch,
+// 36 + 8, lost to 29).  No default may use scratch (bagua_minmax_u8_resident_cfg_info,
 // test_default_rows_use_no_scratch).
 template <typename T>
-constexpr int resident_default_cfg() {
-    return kResDefaultCfg;
-}
+constexpr int resident_default_cfg();
 template <>
 constexpr int resident_default_cfg<F32>() {
     return 32;
@@ -1198,61 +1106,33 @@ static size_t resident_lds_bytes(const ResidentCfg& c) {
     return (size_t)c.h * c.block * 16 + 16 * ((2 * (c.block / kWave) + 4 + 3) / 4);
 }
 
+using ResidentKernel = void (*)(ResidentArgs);
+
+// the kernel of row CFG: its order's entry point with the row's parameters
 template <typename T, int CFG>
-static void* resident_kernel_ptr() {
+static ResidentKernel resident_kernel_ptr() {
     constexpr ResidentCfg c = kResCfg[CFG];
     if constexpr (c.rl != 0)
-        return reinterpret_cast<void*>(&minmax_resident_encode_kernel_window<T, c.block, c.r, c.h, c.rl, c.sb, c.ntm>);
+        return &minmax_resident_encode_kernel_window<T, c.block, c.r, c.h, c.rl, c.sb, c.ntm>;
     else if constexpr (c.stack != 0)
-        return reinterpret_cast<void*>(
-            &minmax_resident_encode_kernel_stack<T, c.block, c.r, c.h, c.sb, c.ntm, (c.stack & 2) != 0, (c.stack & 4) != 0>);
+        return &minmax_resident_encode_kernel_stack<T, c.block, c.r, c.h, c.sb, c.ntm, (c.stack & 2) != 0,
+                                                    (c.stack & 4) != 0>;
     else
-        return reinterpret_cast<void*>(&minmax_resident_encode_kernel<T, c.block, c.r, c.h, c.sb, c.ntm>);
+        return &minmax_resident_encode_kernel<T, c.block, c.r, c.h, c.sb, c.ntm>;
 }
 
+// One table per dtype, built from kResCfg: a new row there needs no other edit.
+template <typename T, size_t... I>
+static ResidentKernel resident_kernel_at(int cfg, std::index_sequence<I...>) {
+    static const ResidentKernel table[] = {resident_kernel_ptr<T, (int)I>()...};
+    return table[cfg];
+}
+
+// nullptr: no such row
 template <typename T>
-static void* resident_kernel_for(int cfg) {
-    switch (cfg) {
-        case 0: return resident_kernel_ptr<T, 0>();
-        case 1: return resident_kernel_ptr<T, 1>();
-        case 2: return resident_kernel_ptr<T, 2>();
-        case 3: return resident_kernel_ptr<T, 3>();
-        case 4: return resident_kernel_ptr<T, 4>();
-        case 5: return resident_kernel_ptr<T, 5>();
-        case 6: return resident_kernel_ptr<T, 6>();
-        case 7: return resident_kernel_ptr<T, 7>();
-        case 8: return resident_kernel_ptr<T, 8>();
-        case 9: return resident_kernel_ptr<T, 9>();
-        case 10: return resident_kernel_ptr<T, 10>();
-        case 11: return resident_kernel_ptr<T, 11>();
-        case 12: return resident_kernel_ptr<T, 12>();
-        case 13: return resident_kernel_ptr<T, 13>();
-        case 14: return resident_kernel_ptr<T, 14>();
-        case 15: return resident_kernel_ptr<T, 15>();
-        case 16: return resident_kernel_ptr<T, 16>();
-        case 17: return resident_kernel_ptr<T, 17>();
-        case 18: return resident_kernel_ptr<T, 18>();
-        case 19: return resident_kernel_ptr<T, 19>();
-        case 20: return resident_kernel_ptr<T, 20>();
-        case 21: return resident_kernel_ptr<T, 21>();
-        case 22: return resident_kernel_ptr<T, 22>();
-        case 23: return resident_kernel_ptr<T, 23>();
-        case 24: return resident_kernel_ptr<T, 24>();
-        case 25: return resident_kernel_ptr<T, 25>();
-        case 26: return resident_kernel_ptr<T, 26>();
-        case 27: return resident_kernel_ptr<T, 27>();
-        case 28: return resident_kernel_ptr<T, 28>();
-        case 29: return resident_kernel_ptr<T, 29>();
-        case 30: return resident_kernel_ptr<T, 30>();
-        case 31: return resident_kernel_ptr<T, 31>();
-        case 32: return resident_kernel_ptr<T, 32>();
-    }
-    return nullptr;
-}
-
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return (e && *e) ? atoi(e) : dflt;
+static ResidentKernel resident_kernel_for(int cfg) {
+    if (cfg < 0 || cfg >= kResNumCfg) return nullptr;
+    return resident_kernel_at<T>(cfg, std::make_index_sequence<kResNumCfg>{});
 }
 
 // Per-device state (slot array zeroed once); false when the resident path is
@@ -1356,7 +1236,8 @@ static int acquire_slot_locked(int dev, hipStream_t s) {
 // runs the two-kernel encode)
 struct ResidentPlan {
     bool ok = false;
-    int cfg = 0;
+    ResidentKernel kern = nullptr;
+    int block = 0;
     int dev = 0;
     size_t lds = 0;
     ResidentArgs a{};
@@ -1367,8 +1248,8 @@ static ResidentPlan resident_plan(const void* input, int64_t in_num_elem, int64_
                                   int64_t out_bytes, int target, hipStream_t s) {
     using S = typename T::storage;
     ResidentPlan pl;
-    const int cfg = env_int("BAGUA_RESIDENT_CFG", resident_default_cfg<T>());
-    if (env_int("BAGUA_RESIDENT", 1) == 0 || cfg < 0 || cfg >= kResNumCfg || p <= 0) return pl;
+    const int cfg = tune_int("BAGUA_RESIDENT_CFG", resident_default_cfg<T>());
+    if (tune_int("BAGUA_RESIDENT", 1) == 0 || cfg < 0 || cfg >= kResNumCfg || p <= 0) return pl;
     {
         std::lock_guard<std::mutex> lk(g_res_mu);
         if (resident_off_streams().count(s)) return pl;
@@ -1380,7 +1261,7 @@ static ResidentPlan resident_plan(const void* input, int64_t in_num_elem, int64_
     // below ~12 Mi elements the fixed cost of the exchange (~4 us: publish + sweep across
     // XCDs) and of starting one 512-thread workgroup per CU (~3 us) loses to the
     // two-kernel encode (crossover between 8 Mi and 16 Mi)
-    if (cs * nact < env_int("BAGUA_RESIDENT_MIN_ELEMS", 12 << 20)) return pl;
+    if (cs * nact < tune_int("BAGUA_RESIDENT_MIN_ELEMS", 12 << 20)) return pl;
     for (int i = 0; i < nact; ++i) {
         const int c = target < 0 ? i : target;
         const uintptr_t src = (uintptr_t)(static_cast<const S*>(input) + (int64_t)c * cs);
@@ -1398,7 +1279,8 @@ static ResidentPlan resident_plan(const void* input, int64_t in_num_elem, int64_
     }
     if (nact > grid) return pl;
     const ResidentCfg& c = kResCfg[cfg];
-    void* kern = resident_kernel_for<T>(cfg);
+    const ResidentKernel kern = resident_kernel_for<T>(cfg);
+    const void* kfn = reinterpret_cast<const void*>(kern);
     const size_t lds = resident_lds_bytes(c);
     {
         // once per (device, dtype, configuration): dynamic LDS above the default, and
@@ -1408,8 +1290,8 @@ static ResidentPlan resident_plan(const void* input, int64_t in_num_elem, int64_
         int& st = admitted[dev][cfg];
         if (st == 0) {
             int per_cu = 0;
-            st = (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                  hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, c.block, lds) == hipSuccess &&
+            st = (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
+                  hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, c.block, lds) == hipSuccess &&
                   per_cu >= 1)
                      ? 1
                      : -1;
@@ -1434,10 +1316,11 @@ static ResidentPlan resident_plan(const void* input, int64_t in_num_elem, int64_
     // at as little as 0.5 TB/s before giving up (then the waiting workgroups
     // re-read the missing slices themselves)
     const int64_t active_bytes = cs * nact * (int64_t)sizeof(S);
-    const int64_t us = env_int("BAGUA_RESIDENT_TIMEOUT_US", (int)(200 + active_bytes / 500000));
+    const int64_t us = tune_int("BAGUA_RESIDENT_TIMEOUT_US", (int)(200 + active_bytes / 500000));
     a.timeout_ticks = (uint64_t)(us < 0 ? 0 : us) * (uint64_t)khz / 1000u;
     a.trace = g_res_trace;
-    pl.cfg = cfg;
+    pl.kern = kern;
+    pl.block = c.block;
     pl.lds = lds;
     pl.dev = dev;
     pl.ok = true;
@@ -1464,59 +1347,7 @@ int resident_compress_impl(const void* input, int64_t in_num_elem, int64_t cs, i
     if (cap != hipStreamCaptureStatusNone) d.state[idx].captured = true;
     pl.a.slot = d.slots + idx;
     const ResidentArgs& a = pl.a;
-    switch (pl.cfg) {
-#define BAGUA_RES_LAUNCH(I)                                                                                 \
-    case I: {                                                                                               \
-        constexpr ResidentCfg k = kResCfg[I];                                                               \
-        if constexpr (k.rl != 0)                                                                            \
-            launch(minmax_resident_encode_kernel_window<T, k.block, k.r, k.h, k.rl, k.sb, k.ntm>,           \
-                   dim3(a.grid), dim3(k.block), (uint32_t)pl.lds, s, a);                                    \
-        else if constexpr (k.stack != 0)                                                                    \
-            launch(minmax_resident_encode_kernel_stack<T, k.block, k.r, k.h, k.sb, k.ntm, (k.stack & 2) != 0, \
-                                                       (k.stack & 4) != 0>,                                 \
-                   dim3(a.grid), dim3(k.block), (uint32_t)pl.lds, s, a);                                    \
-        else                                                                                                \
-            launch(minmax_resident_encode_kernel<T, k.block, k.r, k.h, k.sb, k.ntm>, dim3(a.grid),          \
-                   dim3(k.block), (uint32_t)pl.lds, s, a);                                                  \
-        break;                                                                                              \
-    }
-        BAGUA_RES_LAUNCH(0)
-        BAGUA_RES_LAUNCH(1)
-        BAGUA_RES_LAUNCH(2)
-        BAGUA_RES_LAUNCH(3)
-        BAGUA_RES_LAUNCH(4)
-        BAGUA_RES_LAUNCH(5)
-        BAGUA_RES_LAUNCH(6)
-        BAGUA_RES_LAUNCH(7)
-        BAGUA_RES_LAUNCH(8)
-        BAGUA_RES_LAUNCH(9)
-        BAGUA_RES_LAUNCH(10)
-        BAGUA_RES_LAUNCH(11)
-        BAGUA_RES_LAUNCH(12)
-        BAGUA_RES_LAUNCH(13)
-        BAGUA_RES_LAUNCH(14)
-        BAGUA_RES_LAUNCH(15)
-        BAGUA_RES_LAUNCH(16)
-        BAGUA_RES_LAUNCH(17)
-        BAGUA_RES_LAUNCH(18)
-        BAGUA_RES_LAUNCH(19)
-        BAGUA_RES_LAUNCH(20)
-        BAGUA_RES_LAUNCH(21)
-        BAGUA_RES_LAUNCH(22)
-        BAGUA_RES_LAUNCH(23)
-        BAGUA_RES_LAUNCH(24)
-        BAGUA_RES_LAUNCH(25)
-        BAGUA_RES_LAUNCH(26)
-        BAGUA_RES_LAUNCH(27)
-        BAGUA_RES_LAUNCH(28)
-        BAGUA_RES_LAUNCH(29)
-        BAGUA_RES_LAUNCH(30)
-        BAGUA_RES_LAUNCH(31)
-        BAGUA_RES_LAUNCH(32)
-#undef BAGUA_RES_LAUNCH
-        default:
-            return BAGUA_ERR_UNSUPPORTED;  // a configuration without a launch: never silently skip the encode
-    }
+    launch(pl.kern, dim3(a.grid), dim3(pl.block), (uint32_t)pl.lds, s, a);
     const int rc = check_launch();
     if (rc == BAGUA_OK) d.state[idx].launched += (uint64_t)a.grid;  // each workgroup drains once
     return rc;
@@ -1671,7 +1502,7 @@ extern "C" int bagua_minmax_u8_resident_cfg_info(int dtype, int cfg, int* num_re
     using namespace bagua;
     if (!num_regs || !scratch_bytes) return BAGUA_ERR_INVALID_ARG;
     if (cfg < 0) cfg = bagua_minmax_u8_resident_default_cfg(dtype);
-    void* kern = nullptr;
+    ResidentKernel kern = nullptr;
     switch (dtype) {
         case BAGUA_DTYPE_F32: kern = resident_kernel_for<F32>(cfg); break;
         case BAGUA_DTYPE_F16: kern = resident_kernel_for<F16>(cfg); break;
@@ -1679,7 +1510,7 @@ extern "C" int bagua_minmax_u8_resident_cfg_info(int dtype, int cfg, int* num_re
     }
     if (!kern) return BAGUA_ERR_INVALID_ARG;
     hipFuncAttributes attr{};
-    if (hipFuncGetAttributes(&attr, kern) != hipSuccess) {
+    if (hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kern)) != hipSuccess) {
         g_last_hip_error = (int)hipGetLastError();
         return BAGUA_ERR_HIP;
     }
