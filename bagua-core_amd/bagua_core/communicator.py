@@ -159,14 +159,31 @@ class _LoopbackGroup:
             self.handle = None
 
 
+def _distinct_streams(nranks: int, device_id: int) -> list:
+    """`nranks` streams with `nranks` different handles.  torch hands out streams from a pool
+    of 32 per device and priority, round robin: the 33rd stream requested IS the first one.
+    Two virtual ranks on one stream would share the ops' per-stream workspace (min/max
+    partials, 1-bit tile sums) and race on it from their two threads -- a wrong header now
+    and then.  From 33 ranks on the high-priority pool supplies the other handles."""
+    import torch
+    streams = {}
+    for priority in (0, -1):
+        for _ in range(32):
+            if len(streams) == nranks:
+                break
+            s = torch.cuda.Stream(device=device_id, priority=priority)
+            streams.setdefault(s.cuda_stream, s)
+    if len(streams) < nranks:
+        raise RuntimeError(f"loopback group of {nranks} ranks: only {len(streams)} distinct streams to be had")
+    return list(streams.values())
+
+
 def loopback_communicators(nranks: int, device_id: int = 0) -> list:
     """`nranks` communicators of an in-process loopback group on one device
     (test harness: drive each from its own thread; see bagua_core.h)."""
-    import torch
     group = _LoopbackGroup(nranks, device_id)
     comms = []
-    for r in range(nranks):
-        stream = torch.cuda.Stream(device=device_id)
+    for r, stream in enumerate(_distinct_streams(nranks, device_id)):
         h = N.C.bagua_loopback_communicator_create(group.handle, r, stream.cuda_stream)
         if not h:
             raise RuntimeError("cannot create loopback communicator")
