@@ -15,8 +15,10 @@
 //           min/max; publish the workgroup's {min, max} as two 8-byte
 //           {tag, value} granules (the data is the flag: one atomic store
 //           each, no fence, MI355X guide Guideline 16 R2)
-//   exchange: one wave re-reads the chunk's granules until every tag is this
-//           launch's, folds them (order-free keys, codec_common.hpp)
+//   exchange: two waves poll the chunk's granules, a batch of loads per lane in
+//           flight at once (one memory round trip per round, not one per
+//           granule), until each carries this launch's tag; a granule is kept
+//           once it does; then they are folded (order-free keys, codec_common.hpp)
 //   pass 2: quantise the streamed part first, in reverse (the lines pass 1
 //           read last are the ones the 256 MiB Infinity Cache still holds),
 //           then the LDS part, then the VGPR part, and write header / slack.
@@ -32,7 +34,7 @@
 // Layout of this file: the launch arguments and slice geometry; the per-vector and
 // per-chunk pieces (fold_vec, write_extras, sweep_chunk, fold_missing_slices); the shared
 // phases, each written once as a forced-inline template over the caller's register arrays
-// (draw_tag, load_rows, fold_rows, fold_and_park, fold_stream_ascending, publish_partials,
+// (draw_ticket, park_tag, load_rows, fold_rows, fold_and_park, fold_stream_ascending, publish_partials,
 // exchange_minmax, quant_rows, quant_parked, quant_top_tile, quant_stream_descending /
 // _ascending, finish); the three kernels, each a sequence of those phases in its own order
 // with its own scheduling barriers and trace stamps; then the host side: slots, kResCfg,
@@ -45,7 +47,13 @@
 // drain count below) are spread over kResLanes counters on separate 128-B lines,
 // workgroup g on counter g % kResLanes (its XCD under round-robin placement):
 // 256 returning atomics on ONE word serialise at the memory side (≈ 88 per µs,
-// MI355X guide "dequeue"), which held the last workgroup's start ~3 µs back.  Every workgroup bumps a
+// MI355X guide "dequeue"), which held the last workgroup's start ~3 µs back.  Thread 0 draws the
+// ticket at kernel entry.  In the stack order nothing waits for it there: it is in flight with the
+// first loads of pass 1, turned into the tag in LDS behind them, and read by every thread at the
+// publish, where a barrier already stands.  In the window and stream-last orders thread 0's wave
+// still waits for it (and divides) before its first load, because deferring it lost time there
+// (see those kernels); no order has an LDS broadcast or a barrier ahead of its first loads, and
+// idle workgroups never wait for the value.  Every workgroup bumps a
 // second counter once it is done with the slot (after the exchange), so the
 // host can tell when every launch it issued on a slot has let go of it; a
 // slot changes owner (release, or LRU reclaim when all 64 are taken) only then.
@@ -115,9 +123,16 @@ __device__ __forceinline__ void trace_stamp(const ResidentArgs& a, int g, int k)
 
 // every launch on a slot has the same grid, so counter c receives the same number
 // of tickets per launch: the workgroups g < grid with g % kResLanes == c
+// (the result is never 0, the zeroed state).  The tag is resolved on the publish path, so a
+// counter's first 2^32 tickets divide in 32 bits: the same value as the 64-bit expression
+// below, without its ~100 instructions.
 __device__ __forceinline__ uint32_t tag_of_ticket(uint64_t ticket, int grid, int lane) {
-    const uint64_t per_launch = (uint64_t)((grid - lane + kResLanes - 1) / kResLanes);
-    return (uint32_t)((ticket / per_launch) % 0xffffffffull) + 1u;  // never 0 (the zeroed state)
+    const uint32_t per_launch = (uint32_t)((grid - lane + kResLanes - 1) / kResLanes);
+    if ((ticket >> 32) == 0) {
+        const uint32_t k = (uint32_t)ticket / per_launch;
+        return (k == 0xffffffffu ? 0u : k) + 1u;
+    }
+    return (uint32_t)((ticket / (uint64_t)per_launch) % 0xffffffffull) + 1u;
 }
 
 template <typename T, int BLOCK>
@@ -222,29 +237,57 @@ __device__ void write_extras(const ResidentArgs& a, const SliceGeom<T, BLOCK>& s
         s.payload[j] = (uint8_t)quant(T::to_f(s.src[j]), q);
 }
 
-// one wave folds the granules of active chunk `cl`; false once `deadline` passes
-__device__ __forceinline__ bool sweep_chunk(const ResidentArgs& a, int cl, uint32_t tag, uint64_t deadline,
+// Waves 0 and 1 fold the granules of active chunk `cl`, wave w those with index w * 64 + l + 128 j
+// (l the lane); false once `deadline` passes.  A batch of kSweepBatch granules per lane is
+// requested back to back and waited for once, so a round costs one memory round trip per 512
+// granules (one for a grid of up to 256 workgroups) instead of one per granule.  Two waves,
+// because eight granules in flight per lane made the f32 R = 52 stack rows (24 is pinned by
+// test_default_rows_use_no_scratch) spill.  (The f16 and bf16 R = 52 stack rows, not defaults, which
+// spilled before, spill a few VGPRs more: 41 -> 48 and 33 -> 40 for f16, 0 -> 2-4 for bf16.)
+// The outer loop over batches runs more than once only for more than 256 workgroups per chunk:
+// kResMaxGrid allows it, no 256-CU part reaches it, and it is untested.
+// A granule that carries this launch's tag is final, since a workgroup publishes once per launch:
+// it is folded into the lane's key once and not read again, so the polling thins out as
+// workgroups publish.
+constexpr int kSweepWaves = 2;
+constexpr int kSweepBatch = 4;
+__device__ __forceinline__ bool sweep_chunk(const ResidentArgs& a, int cl, uint32_t tag, int w, uint64_t deadline,
                                             uint32_t& lo, uint32_t& hi, bool bounded) {
     const int lane = lane_id();
-    const uint64_t* g = a.slot->gran + 2 * (int64_t)cl * a.bpc;
+    const uint64_t* g = a.slot->gran + 2 * (int64_t)cl * a.bpc;  // uniform: the lane's part is a 32-bit offset
     const int n = 2 * a.bpc;
-    for (;;) {
-        bool ok = true;
-        uint32_t l = 0xffffffffu, h = 0xffffffffu;
-        for (int i = lane; i < n; i += kWave) {
-            const uint64_t x = __hip_atomic_load(g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok &= (uint32_t)(x >> 32) == tag;
-            if (i & 1) h = min(h, (uint32_t)x);
-            else l = min(l, (uint32_t)x);
+    const int first = w * kWave + lane;
+    // even granules are minima and odd ones maxima, and the lane's are odd when the lane is: one key
+    uint32_t key = 0xffffffffu;
+    for (int base = first; base - first < n; base += kSweepBatch * kSweepWaves * kWave) {
+        uint32_t missing = 0;  // bit j: granule base + 128 j is still to come
+#pragma unroll
+        for (int j = 0; j < kSweepBatch; ++j)
+            if (base + j * kSweepWaves * kWave < n) missing |= 1u << j;
+        for (;;) {
+            uint64_t x[kSweepBatch];
+#pragma unroll
+            for (int j = 0; j < kSweepBatch; ++j) {
+                x[j] = 0;  // tag 0: never this launch's
+                if ((missing >> j) & 1u)
+                    x[j] = __hip_atomic_load(g + (uint32_t)(base + j * kSweepWaves * kWave), __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT);
+            }
+#pragma unroll
+            for (int j = 0; j < kSweepBatch; ++j) {
+                if ((uint32_t)(x[j] >> 32) == tag) {
+                    key = min(key, (uint32_t)x[j]);
+                    missing &= ~(1u << j);
+                }
+            }
+            if (__all(missing == 0)) break;
+            if (bounded && (uint64_t)wall_clock64() > deadline) return false;
+            __builtin_amdgcn_s_sleep(2);
         }
-        if (__all(ok)) {
-            lo = wave_umin(l);
-            hi = wave_umin(h);
-            return true;
-        }
-        if (bounded && (uint64_t)wall_clock64() > deadline) return false;
-        __builtin_amdgcn_s_sleep(2);
     }
+    lo = wave_umin((lane & 1) ? 0xffffffffu : key);
+    hi = wave_umin((lane & 1) ? key : 0xffffffffu);
+    return true;
 }
 
 // after a give-up: the calling thread's share of the chunk's min/max, taking a
@@ -289,20 +332,64 @@ __device__ void fold_missing_slices(const ResidentArgs& a, int cl, uint32_t tag,
 //
 // The words after the parked rows in LDS (`scratch`, W = BLOCK / kWave): [0, W) per-wave min
 // keys, [W, 2W) per-wave max keys, 2W the launch's tag, 2W + 1 whether the exchange completed,
-// 2W + 2 and 2W + 3 the chunk's min and max keys.
+// 2W + 2 + 2i and 2W + 3 + 2i the min and max keys sweeping wave i found (after a give-up: the
+// chunk's), then two words for the traced kernel-entry time.
+constexpr int res_scratch_words(int block) { return 2 * (block / kWave) + 2 + 2 * kSweepWaves + 2; }
 
-// the workgroup's ticket on counter `lane_c` of its slot, as the launch's tag (the same in
-// every thread)
+// Trace stamp 0, kernel entry.  An active workgroup keeps it in LDS until stamp 1, so that no
+// store to memory is pending when the counted waits of pass 1's first loads begin (stores and
+// loads share vmcnt but need not return in order, so the compiler may then wait for everything).
 template <int BLOCK>
-__device__ __forceinline__ uint32_t draw_tag(const ResidentArgs& a, int lane_c, int t, uint32_t* scratch) {
+__device__ __forceinline__ void trace_entry(const ResidentArgs& a, int t, uint32_t* scratch) {
+    constexpr int W = BLOCK / kWave;
+    if (a.trace != nullptr && t == 0) {
+        const uint64_t now = wall_clock64();
+        scratch[2 * W + 2 + 2 * kSweepWaves] = (uint32_t)now;
+        scratch[2 * W + 3 + 2 * kSweepWaves] = (uint32_t)(now >> 32);
+    }
+}
+
+// stamp 0 from LDS (thread 0 wrote it and reads it)
+template <int BLOCK>
+__device__ __forceinline__ void trace_entry_flush(const ResidentArgs& a, int g, int t,
+                                                  const uint32_t* scratch) {
+    constexpr int W = BLOCK / kWave;
+    if (a.trace != nullptr && t == 0)
+        a.trace[8 * g] = ((uint64_t)scratch[2 * W + 3 + 2 * kSweepWaves] << 32) | scratch[2 * W + 2 + 2 * kSweepWaves];
+}
+
+// The workgroup's ticket on counter `lane_c` of its slot, drawn by thread 0 at kernel entry.
+// Nothing waits for it in here; the caller decides where the value is first used (park_tag): the
+// stack order behind its first loads, the window and stream-last orders at once.
+__device__ __forceinline__ uint64_t draw_ticket(const ResidentArgs& a, int lane_c, int t) {
+    uint64_t ticket = 0;
+    if (t == 0) {
+        // The offset is 0, but opaque to the compiler: with an address it knows to be uniform it
+        // rewrites the atomic as a wave-wide one whose result goes through v_readfirstlane, and
+        // that is a full wait (vmcnt(0)) right here (seen with ROCm 7.2's clang 22.0.0git; without
+        // that rewrite the offset costs one v_mov and changes nothing).
+        int zero = 0;
+        asm volatile("" : "+v"(zero));
+        ticket = __hip_atomic_fetch_add(&a.slot->ticket[lane_c][zero], (uint64_t)1, __ATOMIC_RELAXED,
+                                        __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return ticket;
+}
+
+// Once the first loads of pass 1 are issued, thread 0 turns the ticket into the launch's tag and
+// leaves it in LDS (word 2W; word 2W + 1: the exchange counts as complete until a sweeping wave
+// says otherwise).  The wait for the ticket is a counted one that leaves those loads in flight --
+// memory answers in order, so they could not be used earlier anyway -- and the division runs
+// under their latency; the ticket holds no registers across pass 1.  Every thread reads the tag
+// behind the publish's barrier (publish_partials).
+template <int BLOCK>
+__device__ __forceinline__ void park_tag(const ResidentArgs& a, uint64_t ticket, int lane_c, int t,
+                                         uint32_t* scratch) {
     constexpr int W = BLOCK / kWave;
     if (t == 0) {
-        const uint64_t ticket = __hip_atomic_fetch_add(&a.slot->ticket[lane_c][0], (uint64_t)1, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
         scratch[2 * W] = tag_of_ticket(ticket, a.grid, lane_c);
+        scratch[2 * W + 1] = 1u;
     }
-    __syncthreads();
-    return scratch[2 * W];
 }
 
 // the workgroup is done with the slot (once per workgroup, idle ones included)
@@ -416,37 +503,41 @@ __device__ __forceinline__ void workgroup_umin(uint32_t& lo, uint32_t& hi, int t
     }
 }
 
-// end of pass 1: the workgroup's {min, max} as two 8-byte {tag, value} granules
+// end of pass 1: the launch's tag, read here from LDS (park_tag wrote it; the barrier is
+// workgroup_umin's) and returned in every thread, and the workgroup's {min, max} as two 8-byte {tag, value} granules
 template <int BLOCK>
-__device__ __forceinline__ void publish_partials(const ResidentArgs& a, int g, uint32_t tag, uint32_t lo, uint32_t hi,
-                                                 int t, int w, uint32_t* scratch) {
+__device__ __forceinline__ uint32_t publish_partials(const ResidentArgs& a, int g, uint32_t lo, uint32_t hi,
+                                                     int t, int w, uint32_t* scratch) {
+    constexpr int W = BLOCK / kWave;
     workgroup_umin<BLOCK>(lo, hi, t, w, scratch);
+    const uint32_t tag = scratch[2 * W];
     if (t == 0) {
         uint64_t* mine = a.slot->gran + 2 * (int64_t)g;
         __hip_atomic_store(mine, ((uint64_t)tag << 32) | lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(mine + 1, ((uint64_t)tag << 32) | hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    return tag;
 }
 
 struct MinMax {
     float mn, mx;
 };
 
-// The exchange: wave 0 sweeps the granules of active chunk `cl` until every tag is this
+// The exchange: waves 0 and 1 sweep the granules of active chunk `cl` until every tag is this
 // launch's or the deadline passes; on a give-up the whole workgroup folds the missing slices
 // itself (fold_missing_slices; LEAN as there).  The chunk's min/max, the same in every thread.
 template <typename T, int BLOCK, bool LEAN>
 __device__ __forceinline__ MinMax exchange_minmax(const ResidentArgs& a, int cl, uint32_t tag, int t, int w,
                                                   uint32_t* scratch) {
     constexpr int W = BLOCK / kWave;
-    if (w == 0) {
+    if (w < kSweepWaves) {
         const uint64_t deadline = wall_clock64() + a.timeout_ticks;
         uint32_t l = 0, h = 0;
-        const bool ok = sweep_chunk(a, cl, tag, deadline, l, h, true);
+        const bool ok = sweep_chunk(a, cl, tag, w, deadline, l, h, true);
         if (lane_id() == 0) {
-            scratch[2 * W + 1] = ok ? 1u : 0u;
-            scratch[2 * W + 2] = l;
-            scratch[2 * W + 3] = h;
+            if (!ok) scratch[2 * W + 1] = 0u;
+            scratch[2 * W + 2 + 2 * w] = l;
+            scratch[2 * W + 3 + 2 * w] = h;
         }
     }
     __syncthreads();
@@ -456,12 +547,21 @@ __device__ __forceinline__ MinMax exchange_minmax(const ResidentArgs& a, int cl,
         fold_missing_slices<T, BLOCK, LEAN>(a, cl, tag, l, h);
         workgroup_umin<BLOCK>(l, h, t, w, scratch);
         if (t == 0) {
-            scratch[2 * W + 2] = l;
-            scratch[2 * W + 3] = h;
+#pragma unroll
+            for (int i = 0; i < kSweepWaves; ++i) {
+                scratch[2 * W + 2 + 2 * i] = l;
+                scratch[2 * W + 3 + 2 * i] = h;
+            }
         }
         __syncthreads();
     }
-    return MinMax{from_min_space(scratch[2 * W + 2]), from_max_space(scratch[2 * W + 3])};
+    uint32_t cmin = scratch[2 * W + 2], cmax = scratch[2 * W + 3];
+#pragma unroll
+    for (int i = 1; i < kSweepWaves; ++i) {
+        cmin = min(cmin, scratch[2 * W + 2 + 2 * i]);
+        cmax = min(cmax, scratch[2 * W + 3 + 2 * i]);
+    }
+    return MinMax{from_min_space(cmin), from_max_space(cmax)};
 }
 
 // the part of [v0, v1) that lies in the ON_CHIP vectors a slice keeps on chip: a short slice's
@@ -595,7 +695,7 @@ __device__ __forceinline__ void quant_stream_ascending(const uint4* v, int64_t s
 // NTM: non-temporal load mask -- bit 0: pass 2's re-reads of the streamed part;
 // bit 1: pass 1's loads of the part kept on chip (held in VGPRs / parked in LDS), which
 // nothing re-reads, so they need not take Infinity-Cache lines from the streamed part
-// Trace stamps: 0 start, 1 pass 1 end, 2 exchange end, 4 streamed rows stored, 5 parked
+// Trace stamps: 0 entry, 1 pass 1 end, 2 exchange end, 4 streamed rows stored, 5 parked
 // rows stored, 3 end.
 template <typename T, int BLOCK, int R, int H, int SB, int NTM>
 __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(ResidentArgs a) {
@@ -605,17 +705,26 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
     // dynamic LDS only (guide Guideline 17): [H * BLOCK parked vectors][scratch]
     extern __shared__ __attribute__((aligned(16))) uint4 smem[];
     uint4* park = smem;
-    uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // 2*W + 4 words
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // res_scratch_words(BLOCK)
     const int t = (int)threadIdx.x;
     const int g = (int)blockIdx.x;
     const int lane_c = g % kResLanes;  // the workgroup's ticket and drain counter
 
-    const uint32_t tag = draw_tag<BLOCK>(a, lane_c, t, scratch);
-    trace_stamp(a, g, 0);
+    trace_entry<BLOCK>(a, t, scratch);
+    const uint64_t ticket = draw_ticket(a, lane_c, t);
     if (g >= a.nact * a.bpc) {  // idle: the grid is the CU count on every launch of the slot
-        let_go_of_slot(a, lane_c, t);
+        trace_entry_flush<BLOCK>(a, g, t, scratch);
+        let_go_of_slot(a, lane_c, t);  // (the ticket's value is not waited for)
         return;
     }
+    // Unlike the stack order, thread 0's wave WAITS for the ticket here, before its first load.
+    // This order starts pass 1 with R + SB loads per lane (44 at the f32 default); with the ticket
+    // in flight ahead of them and the tag made behind them, as the stack order has it, the
+    // default rows' encode was 0.6 us (f32) and 0.8-1.0 us (bf16) slower with either exchange
+    // (profiles/resident_exchange_ab.jsonl: b_only against parent, ab_all against a_only).  What is left of the
+    // deferral here: the other seven waves start loading at once, with no LDS broadcast and no
+    // barrier, and the division takes its 32-bit path.
+    park_tag<BLOCK>(a, ticket, lane_c, t, scratch);
 
     const SliceGeom<T, BLOCK> s(a, g);
     const uint4* __restrict__ v = reinterpret_cast<const uint4*>(s.src + s.j0);
@@ -649,7 +758,7 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
     }
     if (s.last) fold_scalars<T, BLOCK>(a, s, lo, hi);
     const int w = t / kWave;
-    publish_partials<BLOCK>(a, g, tag, lo, hi, t, w, scratch);
+    const uint32_t tag = publish_partials<BLOCK>(a, g, lo, hi, t, w, scratch);
 
     // the first tile pass 2 re-reads (the top full tile: reverse order) is loaded
     // now, so its latency overlaps the exchange wait instead of following it
@@ -659,6 +768,7 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
     if (nfull2 > 0) load_tile<SB, BLOCK, NT>(v, stream0 + (nfull2 - 1) * tile2, t, pre);
     if (nfull2 > 1) load_tile<SB, BLOCK, NT>(v, stream0 + (nfull2 - 2) * tile2, t, pre2);
 
+    trace_entry_flush<BLOCK>(a, g, t, scratch);
     trace_stamp(a, g, 1);
     const MinMax m = exchange_minmax<T, BLOCK, false>(a, s.cl, tag, t, w, scratch);
     const QParams q = make_qparams(m.mn, m.mx);
@@ -731,10 +841,11 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel(Reside
 //
 // The register budget is max(4R, streaming buffers) + temporaries instead of their
 // sum, which is what lets R grow past 28 at BLOCK = 512 without scratch.
-// EARLY: the first streamed tile is requested before the ticket is drawn (the tag
-// is only needed when the partials are published).
+// EARLY: the first streamed tile is requested before the ticket is drawn (kept for its rows:
+// since this kernel no longer waits for the ticket at its start, it only swaps the first two
+// requests; rows 23 and 24 now measure within 0.15 us of each other, profiles/resident_exchange_ab.jsonl).
 // ASC: pass 2 re-reads the full streamed tiles in pass 1's order.
-// Trace stamps: 0 start, 1 pass 1 end, 2 exchange end, 6 held rows stored,
+// Trace stamps: 0 entry, 1 pass 1 end, 2 exchange end, 6 held rows stored,
 // 7 parked rows stored, 3 end.
 template <typename T, int BLOCK, int R, int H, int SB, int NTM, bool EARLY, bool ASC>
 __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(ResidentArgs a) {
@@ -744,7 +855,7 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
     static_assert(R > 0 && H > 0, "the stack order keeps rows in VGPRs and in LDS");
     extern __shared__ __attribute__((aligned(16))) uint4 smem[];
     uint4* park = smem;
-    uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // 2*W + 4 words
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // res_scratch_words(BLOCK)
     const int t = (int)threadIdx.x;
     const int g = (int)blockIdx.x;
     const int lane_c = g % kResLanes;  // the workgroup's ticket and drain counter
@@ -760,10 +871,11 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
     const int64_t top = stream0 + nfull * tile;  // the ragged top tile [top, v1), possibly empty
 
     uint4 ra[SB];
+    trace_entry<BLOCK>(a, t, scratch);
     if (EARLY && !idle && nfull > 0) load_tile<SB, BLOCK>(v, stream0, t, ra);
-    const uint32_t tag = draw_tag<BLOCK>(a, lane_c, t, scratch);
-    trace_stamp(a, g, 0);
+    const uint64_t ticket = draw_ticket(a, lane_c, t);
     if (idle) {
+        trace_entry_flush<BLOCK>(a, g, t, scratch);
         let_go_of_slot(a, lane_c, t);
         return;
     }
@@ -774,10 +886,9 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
     uint4 held[R];
     if (v1 > v0) {
         uint4 rb[SB];
-        if (nfull > 0) {
-            if (!EARLY) load_tile<SB, BLOCK>(v, stream0, t, ra);
-            fold_stream_ascending<T, BLOCK, SB>(v, stream0, nfull, nfull - 1, t, ra, rb, lo, hi);
-        }
+        if (!EARLY && nfull > 0) load_tile<SB, BLOCK>(v, stream0, t, ra);
+        park_tag<BLOCK>(a, ticket, lane_c, t, scratch);
+        if (nfull > 0) fold_stream_ascending<T, BLOCK, SB>(v, stream0, nfull, nfull - 1, t, ra, rb, lo, hi);
         // the ragged top tile and the first batch of parked rows are requested together
         uint4 cur[SB];
         if (v1 > top) load_rows<SB, 0, BLOCK, false>(v, top, vl, t, rb);
@@ -791,10 +902,13 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
         load_rows<R, 0, BLOCK, NT1>(v, v0, vl, t, held);
         __builtin_amdgcn_sched_barrier(0);
         fold_rows<T, R, true>(held, lo, hi);
+    } else {
+        park_tag<BLOCK>(a, ticket, lane_c, t, scratch);  // an empty slice
     }
     if (s.last) fold_scalars<T, BLOCK>(a, s, lo, hi);
     const int w = t / kWave;
-    publish_partials<BLOCK>(a, g, tag, lo, hi, t, w, scratch);
+    const uint32_t tag = publish_partials<BLOCK>(a, g, lo, hi, t, w, scratch);
+    trace_entry_flush<BLOCK>(a, g, t, scratch);
     trace_stamp(a, g, 1);
 
     // The exchange, written out: exchange_minmax<T, BLOCK, true> is this text, but called as a
@@ -804,14 +918,14 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
     // tests/test_resident_source.py compares the text between the two marks with the helper's.
     constexpr int W = BLOCK / kWave;
     // exchange_minmax: begin
-    if (w == 0) {
+    if (w < kSweepWaves) {
         const uint64_t deadline = wall_clock64() + a.timeout_ticks;
         uint32_t l = 0, h = 0;
-        const bool ok = sweep_chunk(a, s.cl, tag, deadline, l, h, true);
+        const bool ok = sweep_chunk(a, s.cl, tag, w, deadline, l, h, true);
         if (lane_id() == 0) {
-            scratch[2 * W + 1] = ok ? 1u : 0u;
-            scratch[2 * W + 2] = l;
-            scratch[2 * W + 3] = h;
+            if (!ok) scratch[2 * W + 1] = 0u;
+            scratch[2 * W + 2 + 2 * w] = l;
+            scratch[2 * W + 3 + 2 * w] = h;
         }
     }
     __syncthreads();
@@ -821,12 +935,21 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
         fold_missing_slices<T, BLOCK, true>(a, s.cl, tag, l, h);
         workgroup_umin<BLOCK>(l, h, t, w, scratch);
         if (t == 0) {
-            scratch[2 * W + 2] = l;
-            scratch[2 * W + 3] = h;
+#pragma unroll
+            for (int i = 0; i < kSweepWaves; ++i) {
+                scratch[2 * W + 2 + 2 * i] = l;
+                scratch[2 * W + 3 + 2 * i] = h;
+            }
         }
         __syncthreads();
     }
-    const MinMax m{from_min_space(scratch[2 * W + 2]), from_max_space(scratch[2 * W + 3])};
+    uint32_t cmin = scratch[2 * W + 2], cmax = scratch[2 * W + 3];
+#pragma unroll
+    for (int i = 1; i < kSweepWaves; ++i) {
+        cmin = min(cmin, scratch[2 * W + 2 + 2 * i]);
+        cmax = min(cmax, scratch[2 * W + 3 + 2 * i]);
+    }
+    const MinMax m{from_min_space(cmin), from_max_space(cmax)};
     // exchange_minmax: end
     const QParams q = make_qparams(m.mn, m.mx);
     trace_stamp(a, g, 2);
@@ -872,7 +995,7 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
 // by (the stack order puts the whole on-chip part there), so the re-read finds more of
 // its lines in the Infinity Cache; the register budget is
 // 4 RE + max(streaming buffers, 4 RL) + temporaries.
-// Trace stamps: 0 start, 1 pass 1 end, 2 exchange end, 6 late rows stored, 4 streamed
+// Trace stamps: 0 entry, 1 pass 1 end, 2 exchange end, 6 late rows stored, 4 streamed
 // rows stored, 5 parked rows stored, 3 end.
 template <typename T, int BLOCK, int RE, int H, int RL, int SB, int NTM>
 __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_window(ResidentArgs a) {
@@ -882,17 +1005,26 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_window
     static_assert(RE > 0 && H > 0 && RL > 0, "the window order keeps rows in VGPRs (early and late) and in LDS");
     extern __shared__ __attribute__((aligned(16))) uint4 smem[];
     uint4* park = smem;
-    uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // 2*W + 4 words
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(smem + H * BLOCK);  // res_scratch_words(BLOCK)
     const int t = (int)threadIdx.x;
     const int g = (int)blockIdx.x;
     const int lane_c = g % kResLanes;  // the workgroup's ticket and drain counter
 
-    const uint32_t tag = draw_tag<BLOCK>(a, lane_c, t, scratch);
-    trace_stamp(a, g, 0);
+    trace_entry<BLOCK>(a, t, scratch);
+    const uint64_t ticket = draw_ticket(a, lane_c, t);
     if (g >= a.nact * a.bpc) {  // idle: the grid is the CU count on every launch of the slot
-        let_go_of_slot(a, lane_c, t);
+        trace_entry_flush<BLOCK>(a, g, t, scratch);
+        let_go_of_slot(a, lane_c, t);  // (the ticket's value is not waited for)
         return;
     }
+    // Unlike the stack order, thread 0's wave WAITS for the ticket here, before its first load.
+    // This order starts pass 1 with R + SB loads per lane (44 at the f32 default); with the ticket
+    // in flight ahead of them and the tag made behind them, as the stack order has it, the
+    // default rows' encode was 0.6 us (f32) and 0.8-1.0 us (bf16) slower with either exchange
+    // (profiles/resident_exchange_ab.jsonl: b_only against parent, ab_all against a_only).  What is left of the
+    // deferral here: the other seven waves start loading at once, with no LDS broadcast and no
+    // barrier, and the division takes its 32-bit path.
+    park_tag<BLOCK>(a, ticket, lane_c, t, scratch);
 
     const SliceGeom<T, BLOCK> s(a, g);
     const uint4* __restrict__ v = reinterpret_cast<const uint4*>(s.src + s.j0);
@@ -933,7 +1065,8 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_window
     }
     if (s.last) fold_scalars<T, BLOCK>(a, s, lo, hi);
     const int w = t / kWave;
-    publish_partials<BLOCK>(a, g, tag, lo, hi, t, w, scratch);
+    const uint32_t tag = publish_partials<BLOCK>(a, g, lo, hi, t, w, scratch);
+    trace_entry_flush<BLOCK>(a, g, t, scratch);
     trace_stamp(a, g, 1);
 
     const MinMax m = exchange_minmax<T, BLOCK, true>(a, s.cl, tag, t, w, scratch);
@@ -1103,7 +1236,7 @@ constexpr int resident_default_cfg<F16>() {
 }
 
 static size_t resident_lds_bytes(const ResidentCfg& c) {
-    return (size_t)c.h * c.block * 16 + 16 * ((2 * (c.block / kWave) + 4 + 3) / 4);
+    return (size_t)c.h * c.block * 16 + 16 * ((size_t)(res_scratch_words(c.block) + 3) / 4);
 }
 
 using ResidentKernel = void (*)(ResidentArgs);

@@ -68,6 +68,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--elements", type=int, default=1 << 26)
+    ap.add_argument("--dtype", choices=["f32", "f16", "bf16"], default="f32", help="MinMax only")
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--onebit", action="store_true", help="the 1-bit codec (config 3) instead of MinMax")
     a = ap.parse_args()
@@ -88,7 +89,9 @@ def main():
     n = a.elements
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0x5EED)
-    x = torch.randn(n, device=dev, generator=g) * 1e-3
+    dt = {"f32": 0, "f16": 1, "bf16": 2}[a.dtype]  # BAGUA_DTYPE_*
+    assert dt == 0 or not a.onebit
+    x = (torch.randn(n, device=dev, generator=g) * 1e-3).to({0: torch.float32, 1: torch.float16, 2: torch.bfloat16}[dt])
     y = torch.empty_like(x)
     st = torch.cuda.Stream(device=dev)
     sp = ctypes.c_void_p(st.cuda_stream)
@@ -97,18 +100,18 @@ def main():
         S = L0.bagua_onebit_compressed_bytes(n, 1)
         wsb = max(L.bagua_onebit_workspace_bytes(n, 1) for _, L, _ in libs)
     else:
-        S = L0.bagua_minmax_u8_compressed_bytes(0, n, 1)
+        S = L0.bagua_minmax_u8_compressed_bytes(dt, n, 1)
         wsb = max(L.bagua_minmax_u8_workspace_bytes(n, 1) for _, L, _ in libs)
     comp = torch.empty(S, dtype=torch.uint8, device=dev)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
 
     def enc(L):
         f = L.bagua_onebit_compress if a.onebit else L.bagua_minmax_u8_compress
-        return f(0, x.data_ptr(), n, n, 1, comp.data_ptr(), S, ws.data_ptr(), wsb, -1, sp)
+        return f(dt, x.data_ptr(), n, n, 1, comp.data_ptr(), S, ws.data_ptr(), wsb, -1, sp)
 
     def dec(L):
         f = L.bagua_onebit_decompress if a.onebit else L.bagua_minmax_u8_decompress
-        return f(0, comp.data_ptr(), S, n, 1, y.data_ptr(), sp)
+        return f(dt, comp.data_ptr(), S, n, 1, y.data_ptr(), sp)
 
     torch.cuda.synchronize()
     ref = None
@@ -182,9 +185,9 @@ def main():
         for k in range(steps):
             L.bagua_minmax_u8_resident_trace(ctypes.c_void_p(tr[k].data_ptr()))
             L.bagua_time_next_kernel(ev[k][0].cuda_event, ev[k][1].cuda_event)
-            L.bagua_minmax_u8_compress(0, x.data_ptr(), n, n, 1, comp.data_ptr(), S, ws.data_ptr(), wsb, -1, sp)
+            L.bagua_minmax_u8_compress(dt, x.data_ptr(), n, n, 1, comp.data_ptr(), S, ws.data_ptr(), wsb, -1, sp)
             L.bagua_minmax_u8_resident_trace(None)
-            L.bagua_minmax_u8_decompress(0, comp.data_ptr(), S, n, 1, y.data_ptr(), sp)
+            L.bagua_minmax_u8_decompress(dt, comp.data_ptr(), S, n, 1, y.data_ptr(), sp)
         torch.cuda.synchronize()
         dur = np.array([r[0].elapsed_time(r[1]) * 1e3 for r in ev])
         t = tr.cpu().numpy().reshape(steps, cus, 8).astype(np.float64) / 100.0  # 100 MHz wall clock -> us
@@ -197,6 +200,7 @@ def main():
                     "pass1_end_max_us": round(float(u[:, 1].max()), 2),
                     "pass1_end_min_us": round(float(u[:, 1].min()), 2),
                     "exchange_end_max_us": round(float(u[:, 2].max()), 2),
+                    "exchange_after_last_pass1_us": round(float(u[:, 2].max() - u[:, 1].max()), 2),
                     "exchange_wait_max_us": round(float((u[:, 2] - u[:, 1]).max()), 2),
                     "pass2_stream_max_us": round(float((u[:, 4] - u[:, 2]).max()), 2),
                     "end_max_us": round(float(u[:, 3].max()), 2),

@@ -1,6 +1,7 @@
 """Phase timing of the one-launch MinMax encode (minmax_resident.hip) per
 kernel configuration, from the kernel's own wall_clock64 stamps
 (bagua_minmax_u8_resident_trace): pass 1, exchange, pass 2, per workgroup.
+Stamp 0 is kernel entry (before the ticket is drawn), so pass 1 includes the ticket.
 
   python tools/resident_trace.py [--elements N] [--cfgs 0,1,2]
 
@@ -91,6 +92,8 @@ def main():
             "pass1_end_max_us": float(np.median(t[:, :, 1].max(axis=1))),
             "exchange_us_median_wg": float(np.median(t[:, :, 2] - t[:, :, 1])),
             "exchange_end_max_us": float(np.median(t[:, :, 2].max(axis=1))),
+            # from the last workgroup's publish to the last workgroup's leaving the exchange
+            "exchange_after_last_pass1_us": float(np.median(t[:, :, 2].max(axis=1) - t[:, :, 1].max(axis=1))),
             "pass2_us_median_wg": float(np.median(t[:, :, 3] - t[:, :, 2])),
             **{k: float(np.median(v)) for k, v in p2.items()},
             "end_max_us": float(np.median(t[:, :, 3].max(axis=1))),
