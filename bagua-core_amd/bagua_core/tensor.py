@@ -7,7 +7,8 @@ accessors.  Every codec call goes through the C ABI into the gfx950 kernels
 (libbagua_core.so -> libbagua_kernels.so); nothing is computed in Python.
 
 Extensions over the reference: torch.bfloat16 tensors (the reference rejects
-them, lib.rs:211-221) and the "OneBitSignScale" method.
+them, lib.rs:211-221), the "OneBitSignScale" method and the "MXFP4"
+method (MXFP4.md).
 """
 from __future__ import annotations
 
@@ -28,7 +29,8 @@ _DTYPES = {
 _DTYPE_NAMES = {code: name for code, name in _DTYPES.values()}
 _DTYPE_NAMES[N.DTYPE_U64] = "U64"
 
-METHODS = {"MinMaxUInt8": N.COMPRESSION_MINMAX_UINT8, "OneBitSignScale": N.COMPRESSION_ONEBIT}
+METHODS = {"MinMaxUInt8": N.COMPRESSION_MINMAX_UINT8, "OneBitSignScale": N.COMPRESSION_ONEBIT,
+           "MXFP4": N.COMPRESSION_MXFP4}
 
 
 def compression_code(method: str) -> int:

@@ -1,0 +1,476 @@
+// mxfp4.hip — block-scaled 4-bit gradient codec (OCP MXFP4: 32 E2M1 elements under one
+// power-of-two scale byte) for gfx950.  Format and rules: MXFP4.md; the arithmetic of
+// one block: mxfp4_common.hpp.
+//
+// Every block is self-contained, so all three kernels are single streaming passes with
+// no workspace and no LDS:
+//   encode   a lane owns one 16-B input vector (4 f32 / 8 16-bit elements) of each of eight
+//            blocks, loaded together, so a wave's loads are contiguous; the 8 / 4 lanes of
+//            a block share its amax by xor shuffles; 2 / 4 payload bytes per lane
+//   decode   a lane owns one 16-B output vector (4 f32 / 8 16-bit elements: 2 / 4 payload
+//            bytes), four vectors per iteration, so a wave's stores are contiguous
+//   middle   (centralized op) a lane owns one block of the own chunk: it decodes the p
+//            received versions eight elements at a time, sums them in the reference's
+//            tree order (reduce.hip), rounds to T and encodes the 32 results
+//
+// HW = true takes gfx950's conversions (v_cvt_scalef32_pk_fp4_f32 / _pk_f32_fp4) for the
+// rounding to and from E2M1; the scale byte, NaN blocks, the inf and largest-finite
+// clamps and the rounding to T stay in the arithmetic of mxfp4_common.hpp.
+#include <cstdint>
+
+#include "codec_common.hpp"
+#include "launch_util.hpp"
+#include "mxfp4_common.hpp"
+
+namespace bagua {
+
+constexpr int kMxItemBytes = 128;  // input bytes a lane of the encode has in flight per iteration
+constexpr int kMxDecodeVecs = 4;   // 16-B output vectors per lane per decode iteration
+
+template <typename T>
+__device__ __forceinline__ uint32_t mx_nan_bits() {  // canonical quiet NaN of T
+    if constexpr (sizeof(typename T::storage) == 4) return 0x7fc00000u;
+    else if constexpr (T::kDtype == BAGUA_DTYPE_F16) return 0x7e00u;
+    else return 0x7fc0u;
+}
+
+__device__ __forceinline__ int64_t mx_valid(int64_t in_num_elem, int64_t cs, int c) {
+    const int64_t r = in_num_elem - (int64_t)c * cs;
+    return r < 0 ? 0 : (r < cs ? r : cs);
+}
+
+// scale byte and payload words of one block (x: f32 values, invalid elements +0)
+template <bool HW>
+__device__ __forceinline__ void mx_encode(const float (&x)[kMxBlock], float maxf, uint32_t& byte, uint32_t (&w)[4]) {
+    if constexpr (!HW) {
+        mx_encode_block(x, maxf, byte, w);
+    } else {
+        uint32_t am = 0;
+#pragma unroll
+        for (int e = 0; e < kMxBlock; ++e) am = max(am, __float_as_uint(x[e]) & 0x7fffffffu);
+        w[0] = w[1] = w[2] = w[3] = 0u;
+        if (am > 0x7f800000u) {
+            byte = kMxNanScale;
+            return;
+        }
+        byte = mx_scale_byte(min(am, __float_as_uint(maxf)));
+        const float scale = __uint_as_float(byte << 23);  // the conversion reads its exponent: 2^(byte - 127)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            w[k] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w[k], mx_clamp(x[8 * k], maxf), mx_clamp(x[8 * k + 1], maxf), scale, 0);
+            w[k] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w[k], mx_clamp(x[8 * k + 2], maxf), mx_clamp(x[8 * k + 3], maxf), scale, 1);
+            w[k] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w[k], mx_clamp(x[8 * k + 4], maxf), mx_clamp(x[8 * k + 5], maxf), scale, 2);
+            w[k] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w[k], mx_clamp(x[8 * k + 6], maxf), mx_clamp(x[8 * k + 7], maxf), scale, 3);
+        }
+    }
+}
+
+// NB payload bytes (word w, low byte first) of a block with scale byte sb -> 2 * NB values
+// as T stores them (bits; 16-bit patterns zero-extended)
+template <typename T, bool HW, int NB>
+__device__ __forceinline__ void mx_decode(uint32_t w, uint32_t sb, uint32_t (&u)[2 * NB]) {
+    if (sb == kMxNanScale) {
+#pragma unroll
+        for (int e = 0; e < 2 * NB; ++e) u[e] = mx_nan_bits<T>();
+        return;
+    }
+    const float maxf = T::init_max();
+    if constexpr (HW) {
+        typedef float f32x2v __attribute__((ext_vector_type(2)));
+        const float scale = __uint_as_float(sb << 23);
+        f32x2v r[NB];
+        r[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 0);
+        if constexpr (NB > 1) r[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 1);
+        if constexpr (NB > 2) r[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 2);
+        if constexpr (NB > 3) r[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 3);
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            u[2 * k] = stored_bits<T>(mx_clamp(r[k].x, maxf));
+            u[2 * k + 1] = stored_bits<T>(mx_clamp(r[k].y, maxf));
+        }
+    } else {
+        const float hs = mx_half_scale(sb);
+#pragma unroll
+        for (int e = 0; e < 2 * NB; ++e) u[e] = stored_bits<T>(mx_dequant((w >> (4 * e)) & 15u, hs, maxf));
+    }
+}
+
+// ------------------------------------------------------------------------
+// encode: one wave owns a tile of 8 KiB of input as eight wave-wide loads of 1 KiB, issued
+// together (nt: read once); the G = 32 / N neighbouring lanes that hold the N-element
+// vectors of one block share its amax through log2(G) xor shuffles.  A lane holding a
+// whole block instead (eight 16-B loads at a 128-B lane stride) took 116 us for 256 MiB of
+// f32 with nt loads against 49 us here, and 49 us with default-policy loads, which then
+// cost the decode behind it 15 us (profiles/r08_mxfp4_encode_variants.json).
+// ------------------------------------------------------------------------
+template <typename T, bool HW>
+__global__ __launch_bounds__(kBlock) void mxfp4_encode_kernel(const typename T::storage* __restrict__ in,
+                                                             int64_t in_num_elem, int64_t cs, int target,
+                                                             uint8_t* __restrict__ out) {
+    using S = typename T::storage;
+    constexpr int N = Vec<T>::N;        // elements per 16-B vector: 4 / 8
+    constexpr int G = kMxBlock / N;     // lanes per block: 8 / 4
+    constexpr int BW = kWave / G;       // blocks per wave-wide load: 8 / 16
+    constexpr int R = kMxItemBytes / 16;  // loads in flight per lane
+    constexpr int TB = R * BW;          // blocks per wave tile (8 KiB of input)
+    const int c = target < 0 ? (int)blockIdx.y : target;
+    const int64_t n = mx_valid(in_num_elem, cs, c);
+    const S* src = in + (int64_t)c * cs;
+    const bool vec = ((uintptr_t)src % 16) == 0;
+    const int64_t nb = mx_blocks(cs), sbytes = mx_scale_bytes(cs), pbytes = mx_payload_bytes(cs);
+    uint8_t* seg = out + (int64_t)c * (sbytes + pbytes);
+    uint8_t* pay = seg + sbytes;
+    const int lane = lane_id(), sub = lane % G, lb = lane / G;
+    const int64_t tiles = (nb + TB - 1) / TB;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+    const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+    const float maxf = T::init_max();
+    for (int64_t t = wave; t < tiles; t += nwaves) {
+        const int64_t b0 = t * TB;
+        float f[R][N];
+        if (vec && (b0 + TB) * kMxBlock <= n) {
+            uint4 raw[R];
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                const S* p = src + (b0 + k * BW) * kMxBlock + lane * N;
+                raw[k] = nt_load16(p);
+            }
+#pragma unroll
+            for (int k = 0; k < R; ++k) unpack16<T>(raw[k], f[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < R; ++k)
+#pragma unroll
+                for (int e = 0; e < N; ++e) {
+                    const int64_t j = (b0 + k * BW) * kMxBlock + lane * N + e;
+                    f[k][e] = j < n ? T::to_f(src[j]) : 0.0f;
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            uint32_t am = 0;
+#pragma unroll
+            for (int e = 0; e < N; ++e) am = max(am, __float_as_uint(f[k][e]) & 0x7fffffffu);
+#pragma unroll
+            for (int o = 1; o < G; o <<= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, kWave));
+            const int64_t b = b0 + k * BW + lb;
+            if (b >= nb) continue;
+            uint32_t byte = kMxNanScale, w = 0;
+            if (am <= 0x7f800000u) {
+                byte = mx_scale_byte(min(am, __float_as_uint(maxf)));
+                if constexpr (HW) {
+                    const float scale = __uint_as_float(byte << 23);
+                    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(f[k][0], maxf), mx_clamp(f[k][1], maxf), scale, 0);
+                    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(f[k][2], maxf), mx_clamp(f[k][3], maxf), scale, 1);
+                    if constexpr (N == 8) {
+                        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(f[k][4], maxf), mx_clamp(f[k][5], maxf), scale, 2);
+                        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(f[k][6], maxf), mx_clamp(f[k][7], maxf), scale, 3);
+                    }
+                } else {
+                    const float inv = mx_inv_scale(byte);
+#pragma unroll
+                    for (int e = 0; e < N; ++e) w |= mx_quant(mx_clamp(f[k][e], maxf), inv) << (4 * e);
+                }
+            }
+            // plain stores: the payload stays in L2 / the Infinity Cache for its reader
+            if constexpr (N == 4) reinterpret_cast<uint16_t*>(pay + b * kMxBlockBytes)[sub] = (uint16_t)w;
+            else reinterpret_cast<uint32_t*>(pay + b * kMxBlockBytes)[sub] = w;
+            if (sub == 0) {
+                seg[b] = (uint8_t)byte;
+                if (b == nb - 1) {  // slack of both regions, zero
+                    for (int64_t q = nb; q < sbytes; ++q) seg[q] = 0;
+                    if (nb * kMxBlockBytes < pbytes)
+                        *reinterpret_cast<uint4*>(pay + nb * kMxBlockBytes) = make_uint4(0u, 0u, 0u, 0u);
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------
+// decode
+// ------------------------------------------------------------------------
+template <typename T, bool HW, bool NTS>
+__global__ __launch_bounds__(kBlock) void mxfp4_decode_kernel(const uint8_t* __restrict__ in, int64_t cs,
+                                                             typename T::storage* __restrict__ out) {
+    using S = typename T::storage;
+    constexpr int N = Vec<T>::N;
+    constexpr int KV = kMxDecodeVecs;
+    const int c = blockIdx.y;
+    const int64_t sbytes = mx_scale_bytes(cs);
+    const uint8_t* seg = in + (int64_t)c * (sbytes + mx_payload_bytes(cs));
+    const uint8_t* pay = seg + sbytes;
+    S* dst = out + (int64_t)c * cs;
+    const bool vec = ((uintptr_t)dst % 16) == 0;
+    const int64_t nvec = (cs + N - 1) / N;
+    for (int64_t v0 = (int64_t)blockIdx.x * (kBlock * KV) + threadIdx.x; v0 < nvec;
+         v0 += (int64_t)gridDim.x * (kBlock * KV)) {
+        uint32_t w[KV], sb[KV];
+#pragma unroll
+        for (int k = 0; k < KV; ++k) {
+            const int64_t j = (v0 + k * kBlock) * N;
+            w[k] = 0;
+            sb[k] = 0;
+            if (v0 + k * kBlock < nvec) {
+                sb[k] = seg[j / kMxBlock];
+                if constexpr (N == 4) w[k] = *reinterpret_cast<const uint16_t*>(pay + j / 2);
+                else w[k] = *reinterpret_cast<const uint32_t*>(pay + j / 2);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < KV; ++k) {
+            const int64_t j = (v0 + k * kBlock) * N;
+            if (v0 + k * kBlock >= nvec) break;
+            uint32_t u[N];
+            mx_decode<T, HW, N / 2>(w[k], sb[k], u);
+            if (vec && j + N <= cs) {
+                const uint4 q = pack_stored<T>(u);
+                if constexpr (NTS) nt_store16(q, dst + j);
+                else *reinterpret_cast<uint4*>(dst + j) = q;
+            } else {
+#pragma unroll
+                for (int e = 0; e < N; ++e)
+                    if (j + e < cs) dst[j + e] = storage_from_bits<T>(u[e]);
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------
+// fused middle step of the centralized op: decode the p received segments of the own
+// chunk, reduce them as bagua_reduce_chunks does (s[y] = 0 + c[y] + c[y + BY], folded
+// s[y] += s[y + h]; the mean is s / p; rounded to T) and encode the result into the own
+// segment.  Equal, byte for byte, to decompress + bagua_reduce_chunks + compress(target).
+// ------------------------------------------------------------------------
+template <typename T, int BY, bool HW, bool STORE>
+__global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_kernel(const uint8_t* __restrict__ in, int64_t cs, int p,
+                                                                    int average,
+                                                                    typename T::storage* __restrict__ chunk,
+                                                                    uint8_t* __restrict__ out_seg) {
+    constexpr int N = Vec<T>::N;
+    const int64_t nb = mx_blocks(cs), sbytes = mx_scale_bytes(cs), pbytes = mx_payload_bytes(cs);
+    const int64_t segb = sbytes + pbytes;
+    uint8_t* pay_out = out_seg + sbytes;
+    const bool vec = STORE && ((uintptr_t)chunk % 16) == 0;
+    const float pf = (float)p, maxf = T::init_max();
+    for (int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; b < nb; b += (int64_t)gridDim.x * kBlock) {
+        float x[kMxBlock];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {  // eight elements (one payload word) of every segment at a time
+            float s[8][BY];
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+#pragma unroll
+                for (int y = 0; y < BY; ++y) s[e][y] = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {  // p <= 2 * BY
+                uint32_t w[BY], sb[BY];
+#pragma unroll
+                for (int y = 0; y < BY; ++y) {
+                    const int cc = r * BY + y < p ? r * BY + y : p - 1;
+                    const uint8_t* seg = in + (int64_t)cc * segb;
+                    sb[y] = seg[b];
+                    w[y] = reinterpret_cast<const uint32_t*>(seg + sbytes + b * kMxBlockBytes)[q];
+                }
+#pragma unroll
+                for (int y = 0; y < BY; ++y) {
+                    if (r * BY + y >= p) break;
+                    uint32_t u[8];
+                    mx_decode<T, HW, 4>(w[y], sb[y], u);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) s[e][y] = s[e][y] + from_stored_bits<T>(u[e]);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                tree_finish<BY>(s[e]);
+                const int64_t j = b * kMxBlock + q * 8 + e;
+                // the reduced value as stored in T; padding past cs stays +0, as the encoder sees it
+                x[q * 8 + e] = j < cs ? as_stored<T>(average ? s[e][0] / pf : s[e][0]) : 0.0f;
+            }
+        }
+        if constexpr (STORE) {
+            if (vec && (b + 1) * kMxBlock <= cs) {
+#pragma unroll
+                for (int k = 0; k < kMxBlock / N; ++k) {
+                    float f[N];
+#pragma unroll
+                    for (int e = 0; e < N; ++e) f[e] = x[k * N + e];
+                    *reinterpret_cast<uint4*>(chunk + b * kMxBlock + k * N) = pack16<T>(f);
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < kMxBlock; ++e)
+                    if (b * kMxBlock + e < cs) chunk[b * kMxBlock + e] = T::from_f(x[e]);
+            }
+        }
+        uint32_t byte, w[4];
+        mx_encode<HW>(x, maxf, byte, w);
+        out_seg[b] = (uint8_t)byte;
+        *reinterpret_cast<uint4*>(pay_out + b * kMxBlockBytes) = make_uint4(w[0], w[1], w[2], w[3]);
+        if (b == nb - 1) {
+            for (int64_t k = nb; k < sbytes; ++k) out_seg[k] = 0;
+            if (nb * kMxBlockBytes < pbytes)
+                *reinterpret_cast<uint4*>(pay_out + nb * kMxBlockBytes) = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------
+// BAGUA_MXFP4_HWCVT=1 (the default) / 0: the hardware conversions or the arithmetic (A/B; same bytes)
+static bool mx_hw() { return tune_int("BAGUA_MXFP4_HWCVT", 1) != 0; }
+
+static int mx_grid(int64_t items, int64_t per_block, int nact, const char* knob) {
+    int64_t b = (items + per_block - 1) / per_block;
+    const int64_t cap = (tune_int(knob, 2 * kTargetBlocks) + nact - 1) / nact;
+    if (b > cap) b = cap;
+    return (int)(b < 1 ? 1 : b);
+}
+
+template <typename T>
+static int mx_compress_impl(const void* input, int in_num_elem, int cs, int p, uint8_t* out, size_t out_bytes,
+                            int target, hipStream_t s) {
+    using S = typename T::storage;
+    if (p <= 0 || p > 65535 || cs < 0 || in_num_elem < 0 || target < -1 || target >= p || !out || !input)
+        return BAGUA_ERR_INVALID_ARG;
+    if (out_bytes < (size_t)p * (size_t)mx_segment_bytes(cs)) return BAGUA_ERR_INVALID_ARG;
+    if ((uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;  // payload words and the 16-B slack store are aligned stores
+    if (cs == 0) return BAGUA_OK;
+    // a wave tile is 8 KiB of input, a workgroup four of them
+    constexpr int64_t kTileElems = kMxItemBytes * kWave / (int64_t)sizeof(S);
+    const int nact = target < 0 ? p : 1;
+    const dim3 grid(mx_grid(((int64_t)cs + kTileElems - 1) / kTileElems, kWavesPerBlock, nact, "BAGUA_TUNE_MX_ENCODE_BLOCKS"),
+                    nact);
+    if (mx_hw())
+        launch(mxfp4_encode_kernel<T, true>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
+               (int64_t)in_num_elem, (int64_t)cs, target, out);
+    else
+        launch(mxfp4_encode_kernel<T, false>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
+               (int64_t)in_num_elem, (int64_t)cs, target, out);
+    return check_launch();
+}
+
+template <typename T, bool HW>
+static void mx_launch_decode(const dim3& grid, bool nt, const uint8_t* in, int64_t cs, typename T::storage* out,
+                             hipStream_t s) {
+    if (nt) launch(mxfp4_decode_kernel<T, HW, true>, grid, dim3(kBlock), 0, s, in, cs, out);
+    else launch(mxfp4_decode_kernel<T, HW, false>, grid, dim3(kBlock), 0, s, in, cs, out);
+}
+
+template <typename T>
+static int mx_decompress_impl(const uint8_t* in, size_t in_bytes, int cs, int p, void* out, hipStream_t s) {
+    using S = typename T::storage;
+    if (p <= 0 || p > 65535 || cs < 0 || !in || !out) return BAGUA_ERR_INVALID_ARG;
+    if (in_bytes < (size_t)p * (size_t)mx_segment_bytes(cs)) return BAGUA_ERR_INVALID_ARG;
+    if ((uintptr_t)in % 4) return BAGUA_ERR_INVALID_ARG;  // payload read as 2- and 4-B words
+    if (cs == 0) return BAGUA_OK;
+    // store policy by the bucket's size, as the 1-bit decode's (onebit.hip): past the
+    // 256 MiB Infinity Cache the dirty lines cannot stay on chip; BAGUA_MX_DECODE_NT=0 / 1 forces either
+    const int env = tune_int("BAGUA_MX_DECODE_NT", -1);
+    const bool nt = env >= 0 ? env != 0 : (int64_t)cs * p * (int64_t)sizeof(S) > ((int64_t)256 << 20);
+    const int64_t nvec = (cs + Vec<T>::N - 1) / Vec<T>::N;
+    const dim3 grid(mx_grid(nvec, kBlock * kMxDecodeVecs, p, "BAGUA_TUNE_MX_DECODE_BLOCKS"), p);
+    if (mx_hw()) mx_launch_decode<T, true>(grid, nt, in, (int64_t)cs, static_cast<S*>(out), s);
+    else mx_launch_decode<T, false>(grid, nt, in, (int64_t)cs, static_cast<S*>(out), s);
+    return check_launch();
+}
+
+template <typename T, int BY, bool HW>
+static void mx_launch_reduce(int blocks, const uint8_t* in, int64_t cs, int p, int average,
+                             typename T::storage* chunk, uint8_t* seg, hipStream_t s) {
+    if (chunk)
+        launch(mxfp4_reduce_encode_kernel<T, BY, HW, true>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average,
+               chunk, seg);
+    else
+        launch(mxfp4_reduce_encode_kernel<T, BY, HW, false>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average,
+               chunk, seg);
+}
+
+template <typename T, bool HW>
+static void mx_dispatch_reduce(int blocks, const uint8_t* in, int64_t cs, int p, int average,
+                               typename T::storage* chunk, uint8_t* seg, hipStream_t s) {
+    switch (reduce_by(p)) {
+        case 2: mx_launch_reduce<T, 2, HW>(blocks, in, cs, p, average, chunk, seg, s); break;
+        case 4: mx_launch_reduce<T, 4, HW>(blocks, in, cs, p, average, chunk, seg, s); break;
+        default: mx_launch_reduce<T, 8, HW>(blocks, in, cs, p, average, chunk, seg, s); break;
+    }
+}
+
+template <typename T>
+static int mx_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, int cs, int p, void* tensor, int average,
+                                     uint8_t* out, size_t out_bytes, int target, hipStream_t s) {
+    using S = typename T::storage;
+    if (p <= 0 || cs < 0 || target < 0 || target >= p || !recv || !out) return BAGUA_ERR_INVALID_ARG;
+    if (p > kMaxFusedChunks) return BAGUA_ERR_UNSUPPORTED;  // caller runs decompress + reduce + compress
+    const size_t segb = (size_t)mx_segment_bytes(cs);
+    if (recv_bytes < (size_t)p * segb || out_bytes < (size_t)p * segb) return BAGUA_ERR_INVALID_ARG;
+    if ((uintptr_t)recv % 4 || (uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;
+    if (cs == 0) return BAGUA_OK;
+    S* chunk = tensor ? static_cast<S*>(tensor) + (int64_t)target * cs : nullptr;  // nullptr: not stored
+    uint8_t* seg = out + (size_t)target * segb;
+    const int blocks = mx_grid(mx_blocks(cs), kBlock, 1, "BAGUA_TUNE_MX_MIDDLE_BLOCKS");
+    if (mx_hw()) mx_dispatch_reduce<T, true>(blocks, recv, (int64_t)cs, p, average, chunk, seg, s);
+    else mx_dispatch_reduce<T, false>(blocks, recv, (int64_t)cs, p, average, chunk, seg, s);
+    return check_launch();
+}
+
+}  // namespace bagua
+
+using namespace bagua;
+
+extern "C" {
+
+size_t bagua_mxfp4_compressed_bytes(int chunk_size, int num_chunks) {
+    if (chunk_size < 0 || num_chunks < 0) return 0;
+    return (size_t)num_chunks * (size_t)mx_segment_bytes(chunk_size);
+}
+
+int bagua_mxfp4_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                         uint8_t* output, size_t output_bytes, int target_chunk, bagua_stream_t stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case BAGUA_DTYPE_F32:
+            return mx_compress_impl<F32>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
+                                         target_chunk, s);
+        case BAGUA_DTYPE_F16:
+            return mx_compress_impl<F16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
+                                         target_chunk, s);
+        case BAGUA_DTYPE_BF16:
+            return mx_compress_impl<BF16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
+                                          target_chunk, s);
+    }
+    return BAGUA_ERR_UNSUPPORTED;
+}
+
+int bagua_mxfp4_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                           void* output, bagua_stream_t stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case BAGUA_DTYPE_F32: return mx_decompress_impl<F32>(input, input_bytes, chunk_size, num_chunks, output, s);
+        case BAGUA_DTYPE_F16: return mx_decompress_impl<F16>(input, input_bytes, chunk_size, num_chunks, output, s);
+        case BAGUA_DTYPE_BF16: return mx_decompress_impl<BF16>(input, input_bytes, chunk_size, num_chunks, output, s);
+    }
+    return BAGUA_ERR_UNSUPPORTED;
+}
+
+int bagua_mxfp4_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                                  void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
+                                  bagua_stream_t stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case BAGUA_DTYPE_F32:
+            return mx_reduce_requantize_impl<F32>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
+                                                  output_bytes, target_chunk, s);
+        case BAGUA_DTYPE_F16:
+            return mx_reduce_requantize_impl<F16>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
+                                                  output_bytes, target_chunk, s);
+        case BAGUA_DTYPE_BF16:
+            return mx_reduce_requantize_impl<BF16>(input, input_bytes, chunk_size, num_chunks, tensor, average,
+                                                   output, output_bytes, target_chunk, s);
+    }
+    return BAGUA_ERR_UNSUPPORTED;
+}
+
+}  // extern "C"

@@ -1,0 +1,98 @@
+// mxfp4_common.hpp — the arithmetic of the MXFP4 codec (MXFP4.md), one block of 32
+// elements at a time.  Plain integer / IEEE binary32 expressions that give the same bits
+// on the host and on the device, so the rules can be exercised without a GPU
+// (tools/mxfp4_host_check.cpp) and the kernels in mxfp4.hip only add the data movement.
+#pragma once
+
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define MX_HD __host__ __device__ __forceinline__
+#else
+#define MX_HD inline
+#endif
+
+namespace bagua {
+
+constexpr int kMxBlock = 32;        // elements sharing one scale byte
+constexpr int kMxBlockBytes = 16;   // their payload
+constexpr uint32_t kMxNanScale = 0xffu;
+
+MX_HD uint32_t mx_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
+MX_HD float mx_float(uint32_t u) { return __builtin_bit_cast(float, u); }
+
+MX_HD int64_t mx_align32(int64_t v) { return (v + 31) / 32 * 32; }
+MX_HD int64_t mx_blocks(int64_t cs) { return (cs + kMxBlock - 1) / kMxBlock; }
+MX_HD int64_t mx_scale_bytes(int64_t cs) { return mx_align32(mx_blocks(cs)); }
+MX_HD int64_t mx_payload_bytes(int64_t cs) { return mx_align32(kMxBlockBytes * mx_blocks(cs)); }
+MX_HD int64_t mx_segment_bytes(int64_t cs) { return mx_scale_bytes(cs) + mx_payload_bytes(cs); }
+
+// Scale byte e + 127 of a block whose largest |x| has the bits `amax` (finite): with
+// amax = 1.f * 2^(E-127) = m * 2^k, m = 1.f / 2 in [0.5, 1), k = E - 126, the rule
+// e = k - 3 (m <= 0.75) or k - 2 is E - 129 + (fraction > 0.5), and adding 0x3fffff
+// carries into the exponent exactly when the fraction field exceeds 0x400000.
+// Denormal and zero amax (E = 0) clamp to e = -127.
+MX_HD uint32_t mx_scale_byte(uint32_t amax) {
+    const int32_t b = (int32_t)((amax + 0x3fffffu) >> 23) - 2;
+    return b > 0 ? (uint32_t)b : 0u;
+}
+
+// 2^-e for scale byte e + 127 in [0, 253]: biased exponent 254 - byte, always normal
+MX_HD float mx_inv_scale(uint32_t byte) { return mx_float((254u - byte) << 23); }
+
+// 2^(e-1): the factor of the doubled grid 0,1,2,3,4,6,8,12 (2^-128 and 2^-127 are denormal)
+MX_HD float mx_half_scale(uint32_t byte) {
+    return mx_float(byte >= 2u ? (byte - 1u) << 23 : 0x00200000u << byte);
+}
+
+// +-inf -> +-largest finite T, finite values and the sign of zero unchanged (x is no NaN)
+MX_HD float mx_clamp(float x, float maxf) { return __builtin_fminf(__builtin_fmaxf(x, -maxf), maxf); }
+
+// sign << 3 | code of x * 2^-e, |x * 2^-e| <= 6, rounded to the E2M1 grid, ties to the
+// even code.  The grid's step is 0.5 below 2, 1 below 4, 2 below 8: adding M = 2^22 times
+// the step rounds |y| to that step in the add itself (RNE), leaving n = |y| / step in the
+// low bits of the sum and the exponent E' = max(E, 127) + 22 above them, and
+// code = n + 2 * (max(E, 127) - 127).
+MX_HD uint32_t mx_quant(float x, float inv) {
+    const float y = x * inv;
+    const uint32_t yb = mx_bits(y), ya = yb & 0x7fffffffu;
+    const uint32_t mx = ya > 0x3f800000u ? ya : 0x3f800000u;
+    const float m = mx_float((mx & 0x7f800000u) + 0x0b000000u);
+    const uint32_t tb = mx_bits(mx_float(ya) + m);
+    return ((tb & 7u) + (tb >> 22) - 298u) | ((yb >> 28) & 8u);
+}
+
+// twice the grid value of a code
+MX_HD uint32_t mx_grid2(uint32_t code) { return (uint32_t)(0x0C08060403020100ull >> (8u * code)) & 0xffu; }
+
+// the f32 value of a nibble under half scale hs, magnitude clamped to maxf (the product is
+// exact: a 2-bit significand times a power of two, denormals included; past the f32 range
+// it is inf and clamps)
+MX_HD float mx_dequant(uint32_t nib, float hs, float maxf) {
+    const float v = __builtin_fminf((float)mx_grid2(nib & 7u) * hs, maxf);
+    return mx_float(mx_bits(v) | ((nib & 8u) << 28));
+}
+
+// One block: x[32] as f32 (invalid elements already +0) -> scale byte and 16 payload
+// bytes as 4 little-endian words.
+MX_HD void mx_encode_block(const float (&x)[kMxBlock], float maxf, uint32_t& byte, uint32_t (&w)[4]) {
+    uint32_t am = 0;
+#pragma unroll
+    for (int e = 0; e < kMxBlock; ++e) {
+        const uint32_t a = mx_bits(x[e]) & 0x7fffffffu;
+        am = a > am ? a : am;
+    }
+    w[0] = w[1] = w[2] = w[3] = 0u;
+    if (am > 0x7f800000u) {  // a NaN in the block
+        byte = kMxNanScale;
+        return;
+    }
+    const uint32_t mb = mx_bits(maxf);
+    byte = mx_scale_byte(am < mb ? am : mb);
+    const float inv = mx_inv_scale(byte);
+#pragma unroll
+    for (int e = 0; e < kMxBlock; ++e) w[e / 8] |= mx_quant(mx_clamp(x[e], maxf), inv) << (4 * (e % 8));
+}
+
+}  // namespace bagua

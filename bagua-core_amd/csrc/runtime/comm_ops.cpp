@@ -270,6 +270,12 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
                                             (void*)(uintptr_t)ws, ws_bytes, (void*)(uintptr_t)s);
         if (rc == BAGUA_OK) done = true;
         else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
+    } else if (fused && method == BAGUA_COMPRESSION_MXFP4 && t->num_elem == t->num_elem_allocated) {
+        // one kernel, no workspace; the reduced chunk is not stored (step 5 rewrites every element)
+        rc = bagua_mxfp4_reduce_requantize(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, nullptr, average,
+                                           send.as<uint8_t>(), k.S, k.rank, (void*)(uintptr_t)s);
+        if (rc == BAGUA_OK) done = true;
+        else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
     }
     if (!done) {
         TRY(bagua_tensor_decompress_from(t, method, k.p, rview, s));

@@ -213,6 +213,32 @@ int bagua_onebit_reduce_requantize_ef(int dtype, const uint8_t* input, size_t in
                                       float* scale, bagua_stream_t stream);
 
 /* ======================================================================== */
+/* v2 — MXFP4 block-scaled 4-bit codec (extension; format in MXFP4.md)       */
+/* ======================================================================== */
+/* Per chunk: align32(nb) scale bytes, then align32(16*nb) payload bytes, nb =
+ * ceil(chunk_size / 32); S = num_chunks * that.  Single-pass kernels, no workspace.
+ * Segments lie at that fixed stride: the buffers must hold at least S bytes
+ * (BAGUA_ERR_INVALID_ARG otherwise) and be 16-B aligned. */
+size_t bagua_mxfp4_compressed_bytes(int chunk_size, int num_chunks);
+/* target_chunk = -1 encodes every chunk, otherwise only chunk `target_chunk` (the other
+ * segments are left untouched).  Elements at or past input_num_element count as +0
+ * and are not read. */
+int bagua_mxfp4_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                         uint8_t* output, size_t output_bytes, int target_chunk, bagua_stream_t stream);
+int bagua_mxfp4_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                           void* output, bagua_stream_t stream);
+/* Middle step of the centralized op with the MXFP4 codec, fused into one kernel: decode
+ * the num_chunks received segments of `input`, reduce them in the reference's summation
+ * order (mean if `average`), round to T and encode into segment `target_chunk` of
+ * `output`.  Equal, byte for byte, to bagua_mxfp4_decompress + bagua_reduce_chunks +
+ * bagua_mxfp4_compress(target) on a fully valid tensor.  `tensor` (num_chunks *
+ * chunk_size elements) receives the reduced chunk; NULL: it is not stored.
+ * BAGUA_ERR_UNSUPPORTED for num_chunks > 16. */
+int bagua_mxfp4_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                                  void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
+                                  bagua_stream_t stream);
+
+/* ======================================================================== */
 /* v2 — chunk reduction and elementwise ops                                  */
 /* ======================================================================== */
 /* reduce_{mean,sum}_{f32,f16}_inplace_host (K:646-660): chunk target_chunk =
