@@ -9,12 +9,12 @@ from . import _native
 from .backend import BaguaCommBackendPy
 from .bucket import BaguaBucketPy
 from .communicator import BaguaSingleCommunicatorPy
-from .tensor import METHODS, BaguaTensorPy, OneBitErrorFeedbackState
+from .tensor import METHODS, BaguaTensorPy, MXFP4ErrorFeedbackState, OneBitErrorFeedbackState
 
 __version__ = "0.1.0+mi355x"
 
 __all__ = ["BaguaCommBackendPy", "BaguaBucketPy", "BaguaSingleCommunicatorPy", "BaguaTensorPy", "METHODS",
-           "OneBitErrorFeedbackState", "show_version"]
+           "MXFP4ErrorFeedbackState", "OneBitErrorFeedbackState", "show_version"]
 
 
 def show_version() -> None:

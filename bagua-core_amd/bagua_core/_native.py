@@ -61,6 +61,7 @@ class bagua_bucket_op_t(ctypes.Structure):
 BUCKET_OP_CENTRALIZED_LOW_PRECISION, BUCKET_OP_CENTRALIZED_FULL_PRECISION = 1, 2
 BUCKET_OP_DECENTRALIZED_LOW_PRECISION, BUCKET_OP_CALLBACK = 3, 4
 BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK = 5
+BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK = 6
 STATUS_INVALID_ARG = 1
 
 _T = ctypes.POINTER(bagua_tensor_t)
@@ -142,6 +143,9 @@ KERNEL_SIGNATURES = {
     "bagua_mxfp4_compress": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
     "bagua_mxfp4_decompress": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _vp]),
     "bagua_mxfp4_reduce_requantize": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _vp, _sz, _i32, _vp]),
+    "bagua_mxfp4_ef_state_bytes": (_i32, [_i32, _i32, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "bagua_mxfp4_compress_ef": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
+    "bagua_mxfp4_reduce_requantize_ef": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
     "bagua_reduce_chunks": (_i32, [_i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "bagua_add_inplace": (_i32, [_i32, _vp, _vp, _i32, _vp]),
     "bagua_addmul_inplace": (_i32, [_i32, _vp, _vp, _i32, _f32, _vp]),
@@ -192,6 +196,7 @@ CORE_SIGNATURES = {
     "bagua_tensor_compress": (_i32, [_T, _i32, _i32, _u64, _i32, _T]),
     "bagua_tensor_compress_into": (_i32, [_T, _i32, _i32, _u64, _i32, _T]),
     "bagua_tensor_compress_error_feedback": (_i32, [_T, _i32, _u64, _T, _T, _T]),
+    "bagua_tensor_compress_mxfp4_error_feedback": (_i32, [_T, _i32, _u64, _T, _T]),
     "bagua_tensor_decompress_from": (_i32, [_T, _i32, _i32, _T, _u64]),
     "bagua_tensor_reduce_inplace": (_i32, [_T, _i32, _i32, _i32, _u64]),
     "bagua_tensor_add_inplace": (_i32, [_T, _T, _u64]),
@@ -231,6 +236,7 @@ CORE_SIGNATURES = {
     "bagua_centralized_low_precision_synchronous_unfused": (_i32, [_C, _T, _i32, _i32]),
     "bagua_centralized_low_precision_pipelined": (_i32, [_C, _T, _i32, _i32, _i32]),
     "bagua_centralized_onebit_error_feedback": (_i32, [_C, _T, _i32, _T, _T, _T, _T, _i32]),
+    "bagua_centralized_mxfp4_error_feedback": (_i32, [_C, _T, _i32, _T, _T]),
     "bagua_centralized_full_precision_synchronous": (_i32, [_C, _T, _i32]),
     "bagua_decentralized_low_precision_synchronous": (_i32, [_C, _T, _T, _T, _T, _i32]),
     "bagua_decentralized_low_precision_synchronous_unfused": (_i32, [_C, _T, _T, _T, _T, _i32]),

@@ -9,6 +9,7 @@ on the communicator's stream:
 
   CentralizedLowPrecisionSynchronous   -> bagua_centralized_low_precision_synchronous
   CentralizedOneBitErrorFeedback       -> bagua_centralized_onebit_error_feedback
+  CentralizedMXFP4ErrorFeedback        -> bagua_centralized_mxfp4_error_feedback
   CentralizedFullPrecisionSynchronous  -> bagua_centralized_full_precision_synchronous
   DecentralizedLowPrecisionSynchronous -> bagua_decentralized_low_precision_synchronous
   PythonOp                             -> a ctypes callback (python_ffi_op.rs)
@@ -27,7 +28,7 @@ from typing import Callable, Optional
 
 from . import _native as N
 from .communicator import BaguaSingleCommunicatorPy
-from .tensor import _DTYPES, BaguaTensorPy, OneBitErrorFeedbackState, compression_code
+from .tensor import _DTYPES, BaguaTensorPy, MXFP4ErrorFeedbackState, OneBitErrorFeedbackState, compression_code
 
 CALLBACK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_char_p)
 
@@ -67,6 +68,28 @@ class CentralizedOneBitErrorFeedback:
                                    ef_worker_scales=st._raw(st.worker_scales),
                                    ef_server_carry=st._raw(st.server_carry),
                                    ef_server_scale=st._raw(st.server_scale))
+
+
+@dataclass
+class CentralizedMXFP4ErrorFeedback:
+    """the "MXFP4" centralized op carrying its quantisation error from step to step in
+    `state` (kept alive with the op); the residuals travel in the two carry fields"""
+    communicator: BaguaSingleCommunicatorPy
+    average: bool
+    state: MXFP4ErrorFeedbackState
+    compression: str = "MXFP4"
+
+    def native(self) -> N.bagua_bucket_op_t:
+        st = self.state
+        return N.bagua_bucket_op_t(kind=N.BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK, average=int(self.average),
+                                   compression=compression_code(self.compression), fused=1,
+                                   comm=_handle(self.communicator), ef_worker_carry=st._raw(st.worker_residual),
+                                   ef_server_carry=st._raw(st.server_residual))
+
+
+# the state class of each codec that has error feedback, and the op it appends
+_EF_CODECS = {"OneBitSignScale": (OneBitErrorFeedbackState, CentralizedOneBitErrorFeedback),
+              "MXFP4": (MXFP4ErrorFeedbackState, CentralizedMXFP4ErrorFeedback)}
 
 
 @dataclass
@@ -189,9 +212,11 @@ class BaguaBucketPy:
                                           communicator_intranode: Optional[BaguaSingleCommunicatorPy] = None,
                                           hierarchical: bool = False, average: bool = True,
                                           scattergather: bool = False, compression: Optional[str] = None,
-                                          error_feedback: Optional[OneBitErrorFeedbackState] = None) -> None:
-        """error_feedback (keyword; "OneBitSignScale" only, not hierarchical): the state that
-        carries the op's quantisation error from one execution to the next"""
+                                          error_feedback=None) -> None:
+        """error_feedback (keyword; not hierarchical): the state that carries the op's
+        quantisation error from one execution to the next -- a OneBitErrorFeedbackState with
+        "OneBitSignScale", an MXFP4ErrorFeedbackState with "MXFP4".
+        """
         if error_feedback is not None:
             self._append_error_feedback(communicator_internode, hierarchical, average, compression, error_feedback)
             return
@@ -205,15 +230,19 @@ class BaguaBucketPy:
             self._append(CentralizedLowPrecisionSynchronous(comm, average, compression, intranode=intra))
 
     def _append_error_feedback(self, comm, hierarchical, average, compression, state) -> None:
-        if compression != "OneBitSignScale":
-            raise NotImplementedError(f"error feedback exists for the OneBitSignScale codec only, not for "
+        if compression not in _EF_CODECS:
+            raise NotImplementedError(f"error feedback exists for the OneBitSignScale and MXFP4 codecs only, not for "
                                       f"compression={compression!r}")
+        state_cls, op_cls = _EF_CODECS[compression]
+        if isinstance(state, (OneBitErrorFeedbackState, MXFP4ErrorFeedbackState)) and not isinstance(state, state_cls):
+            raise NotImplementedError(f"compression={compression!r} takes a {state_cls.__name__}, not a "
+                                      f"{type(state).__name__}")
         if hierarchical:
             raise NotImplementedError("error feedback is not available in hierarchical mode")
         if comm is None:
             raise RuntimeError("inter node communicator must be given in non-hierarchical mode")
-        if not isinstance(state, OneBitErrorFeedbackState):
-            raise TypeError("error_feedback must be a OneBitErrorFeedbackState")
+        if not isinstance(state, state_cls):
+            raise TypeError(f"error_feedback must be a {state_cls.__name__}")
         if state._op is not None and state._op() is not None:
             raise RuntimeError("this error-feedback state already belongs to another op: one state, one op")
         n = sum(t.num_elements_allocated() for t in self._tensors)
@@ -223,7 +252,7 @@ class BaguaBucketPy:
                                f"device {first.device_id}")
         if first.dtype not in (N.DTYPE_F32, N.DTYPE_F16, N.DTYPE_BF16):
             raise RuntimeError("error feedback needs a floating-point bucket")
-        op = CentralizedOneBitErrorFeedback(comm, average, state)
+        op = op_cls(comm, average, state)
         self._append(op)
         state._op = weakref.ref(op)
 

@@ -176,10 +176,13 @@ class BaguaTensorPy:
         res._used_on(current_stream_ptr(src.device_id))
         return res
 
-    def compress_with_error_feedback(self, n_chunks: int, state: "OneBitErrorFeedbackState") -> "BaguaTensorPy":
-        """compress("OneBitSignScale", n_chunks, -1) of this step's compensated values
-        (DESIGN.md §4): the worker half of `state` (carry, one scale per chunk) is read and
+    def compress_with_error_feedback(self, n_chunks: int, state) -> "BaguaTensorPy":
+        """compress(codec, n_chunks, -1) of this step's compensated values, the codec being the
+        one `state` belongs to: a OneBitErrorFeedbackState ("OneBitSignScale") or an
+        MXFP4ErrorFeedbackState ("MXFP4", MXFP4.md).  The worker half of `state` is read and
         updated in place; the result is the U8 buffer, owned like compress()'s."""
+        if not isinstance(state, (OneBitErrorFeedbackState, MXFP4ErrorFeedbackState)):
+            raise TypeError("state must be a OneBitErrorFeedbackState or an MXFP4ErrorFeedbackState")
         src = self.raw()
         if n_chunks <= 0 or src.num_elem_allocated % n_chunks != 0:
             raise RuntimeError("compression tensor size % n_chunks must be 0")
@@ -189,9 +192,14 @@ class BaguaTensorPy:
                                f"device {src.device_id}")
         out = N.bagua_tensor_t()
         stream = current_stream_ptr(src.device_id)
-        carry, scales = state._raw(state.worker_carry), state._raw(state.worker_scales)
-        rc = N.C.bagua_tensor_compress_error_feedback(ctypes.byref(src), n_chunks, stream, ctypes.byref(carry),
-                                                      ctypes.byref(scales), ctypes.byref(out))
+        if isinstance(state, MXFP4ErrorFeedbackState):
+            residual = state._raw(state.worker_residual)
+            rc = N.C.bagua_tensor_compress_mxfp4_error_feedback(ctypes.byref(src), n_chunks, stream,
+                                                                ctypes.byref(residual), ctypes.byref(out))
+        else:
+            carry, scales = state._raw(state.worker_carry), state._raw(state.worker_scales)
+            rc = N.C.bagua_tensor_compress_error_feedback(ctypes.byref(src), n_chunks, stream, ctypes.byref(carry),
+                                                          ctypes.byref(scales), ctypes.byref(out))
         N.check(rc, f"compress_with_error_feedback(n_chunks={n_chunks})")
         res = BaguaTensorPy._from_raw(out, "compressed_tensor", owned=True)
         res._used_on(stream)
@@ -288,4 +296,41 @@ class OneBitErrorFeedbackState:
 
     def __repr__(self) -> str:
         return (f"OneBitErrorFeedbackState(num_elements={self.num_elements}, nranks={self.nranks}, "
+                f"device_id={self.device_id})")
+
+
+class MXFP4ErrorFeedbackState:
+    """The state of the MXFP4 codec's error feedback for one bucket (MXFP4.md): two
+    zero-initialised float32 device tensors, ordinary torch tensors the caller may
+    checkpoint and restore.
+
+      worker_residual[num_elements]            what this rank encodes
+      server_residual[num_elements / nranks]   the own chunk it re-encodes
+
+    A block's decode is known where it is encoded, so the state is the residual itself:
+    the compensated value minus what the receiver decodes; zero means "no error carried"."""
+
+    def __init__(self, num_elements: int, nranks: int, device_id: int):
+        if nranks <= 0 or num_elements <= 0 or num_elements % nranks != 0:
+            raise ValueError(f"num_elements ({num_elements}) must be a positive multiple of nranks ({nranks})")
+        self.num_elements, self.nranks, self.device_id = int(num_elements), int(nranks), int(device_id)
+        dev = torch.device("cuda", self.device_id)
+        self.worker_residual = torch.zeros(self.num_elements, dtype=torch.float32, device=dev)
+        self.server_residual = torch.zeros(self.num_elements // self.nranks, dtype=torch.float32, device=dev)
+        self._op = None  # the bucket op using this state (one state, one op)
+
+    def tensors(self) -> tuple:
+        return self.worker_residual, self.server_residual
+
+    def zero_(self) -> "MXFP4ErrorFeedbackState":
+        for t in self.tensors():
+            t.zero_()
+        return self
+
+    def _raw(self, t: torch.Tensor) -> N.bagua_tensor_t:
+        n = t.numel()
+        return N.bagua_tensor_t(t.data_ptr(), n, n, N.DTYPE_F32, self.device_id)
+
+    def __repr__(self) -> str:
+        return (f"MXFP4ErrorFeedbackState(num_elements={self.num_elements}, nranks={self.nranks}, "
                 f"device_id={self.device_id})")

@@ -12,6 +12,8 @@
 //   middle   (centralized op) a lane owns one block of the own chunk: it decodes the p
 //            received versions eight elements at a time, sums them in the reference's
 //            tree order (reduce.hip), rounds to T and encodes the 32 results
+// and the two error-feedback kernels, the encode and the middle step with an f32 residual
+// read and rewritten in the same pass (further down).
 //
 // HW = true takes gfx950's conversions (v_cvt_scalef32_pk_fp4_f32 / _pk_f32_fp4) for the
 // rounding to and from E2M1; the scale byte, NaN blocks, the inf and largest-finite
@@ -317,6 +319,263 @@ __global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_kernel(const uint8
 }
 
 // ------------------------------------------------------------------------
+// error feedback (MXFP4.md, "Error feedback"): the encode of v = x + e with the f32 residual
+// e read and rewritten in the same pass, e' = clamp(v) - decode(nibble) as T stores it.  A
+// block's decode is known where it is encoded, so the state is the residual alone.
+// ------------------------------------------------------------------------
+// NE values (one or two payload words' worth, NE / 8 words in w) of a block without NaN:
+// v -> the new residual, in place
+template <typename T, bool HW, int NE>
+__device__ __forceinline__ void mx_residual(float (&v)[NE], const uint32_t* w, uint32_t byte, float maxf) {
+    constexpr int K = T::kDtype;
+    if constexpr (HW) {
+        typedef float f32x2v __attribute__((ext_vector_type(2)));
+        const float scale = __uint_as_float(byte << 23);
+#pragma unroll
+        for (int e = 0; e < NE; e += 8) {
+            f32x2v r[4];
+            r[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w[e / 8], scale, 0);
+            r[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w[e / 8], scale, 1);
+            if constexpr (NE >= 8) {
+                r[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w[e / 8], scale, 2);
+                r[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w[e / 8], scale, 3);
+            }
+#pragma unroll
+            for (int q = 0; q < (NE < 8 ? NE : 8) / 2; ++q) {
+                v[e + 2 * q] = mx_ef_residual<K>(mx_clamp(v[e + 2 * q], maxf), mx_clamp(r[q].x, maxf));
+                v[e + 2 * q + 1] = mx_ef_residual<K>(mx_clamp(v[e + 2 * q + 1], maxf), mx_clamp(r[q].y, maxf));
+            }
+        }
+    } else {
+        const float hs = mx_half_scale(byte);
+#pragma unroll
+        for (int e = 0; e < NE; ++e)
+            v[e] = mx_ef_residual<K>(mx_clamp(v[e], maxf), mx_dequant((w[e / 8] >> (4 * (e % 8))) & 15u, hs, maxf));
+    }
+}
+
+// Worker step: mxfp4_encode_kernel's cooperative layout (a lane owns one 16-B vector of T of
+// each of eight blocks) plus the matching residual, N / 4 16-B f32 vectors per lane-vector.
+// Every chunk is fully valid.  Gradient loads are non-temporal as the plain encode's; the
+// residual's loads and stores are non-temporal when NT (the host picks by the state's size).
+// Chunks whose gradient or residual is not 16-B aligned, and ragged tiles, take guarded
+// element accesses.
+template <typename T, bool HW, bool NT>
+__global__ __launch_bounds__(kBlock) void mxfp4_encode_ef_kernel(const typename T::storage* __restrict__ in,
+                                                                int64_t cs, float* __restrict__ res,
+                                                                uint8_t* __restrict__ out) {
+    using S = typename T::storage;
+    constexpr int N = Vec<T>::N;
+    constexpr int G = kMxBlock / N;
+    constexpr int BW = kWave / G;
+    constexpr int R = kMxItemBytes / 16;
+    constexpr int TB = R * BW;
+    const int c = (int)blockIdx.y;
+    const S* src = in + (int64_t)c * cs;
+    float* rsd = res + (int64_t)c * cs;
+    const bool vecx = ((uintptr_t)src % 16) == 0, vecr = ((uintptr_t)rsd % 16) == 0;
+    const int64_t nb = mx_blocks(cs), sbytes = mx_scale_bytes(cs), pbytes = mx_payload_bytes(cs);
+    uint8_t* seg = out + (int64_t)c * (sbytes + pbytes);
+    uint8_t* pay = seg + sbytes;
+    const int lane = lane_id(), sub = lane % G, lb = lane / G;
+    const int64_t tiles = (nb + TB - 1) / TB;
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+    const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+    const float maxf = T::init_max();
+    for (int64_t t = wave; t < tiles; t += nwaves) {
+        const int64_t b0 = t * TB;
+        const bool full = (b0 + TB) * kMxBlock <= cs;
+        float f[R][N], r[R][N];
+        if (vecx && full) {
+            uint4 raw[R];
+#pragma unroll
+            for (int k = 0; k < R; ++k) raw[k] = nt_load16(src + (b0 + k * BW) * kMxBlock + lane * N);
+#pragma unroll
+            for (int k = 0; k < R; ++k) unpack16<T>(raw[k], f[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < R; ++k)
+#pragma unroll
+                for (int e = 0; e < N; ++e) {
+                    const int64_t j = (b0 + k * BW) * kMxBlock + lane * N + e;
+                    f[k][e] = j < cs ? T::to_f(src[j]) : 0.0f;
+                }
+        }
+        if (vecr && full) {
+#pragma unroll
+            for (int k = 0; k < R; ++k)
+#pragma unroll
+                for (int h = 0; h < N / 4; ++h) {
+                    const float* q = rsd + (b0 + k * BW) * kMxBlock + lane * N + 4 * h;
+                    const uint4 u = NT ? nt_load16(q) : *reinterpret_cast<const uint4*>(q);
+                    r[k][4 * h] = __uint_as_float(u.x);
+                    r[k][4 * h + 1] = __uint_as_float(u.y);
+                    r[k][4 * h + 2] = __uint_as_float(u.z);
+                    r[k][4 * h + 3] = __uint_as_float(u.w);
+                }
+        } else {
+#pragma unroll
+            for (int k = 0; k < R; ++k)
+#pragma unroll
+                for (int e = 0; e < N; ++e) {
+                    const int64_t j = (b0 + k * BW) * kMxBlock + lane * N + e;
+                    r[k][e] = j < cs ? rsd[j] : 0.0f;
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            uint32_t am = 0;
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                r[k][e] = mx_ef_sum(f[k][e], r[k][e]);  // v, and below the new residual
+                am = max(am, __float_as_uint(r[k][e]) & 0x7fffffffu);
+            }
+#pragma unroll
+            for (int o = 1; o < G; o <<= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, kWave));
+            const int64_t b = b0 + k * BW + lb;
+            if (b >= nb) continue;
+            uint32_t byte = kMxNanScale, w = 0;
+            if (am <= 0x7f800000u) {
+                byte = mx_scale_byte(min(am, __float_as_uint(maxf)));
+                if constexpr (HW) {
+                    const float scale = __uint_as_float(byte << 23);
+                    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(r[k][0], maxf), mx_clamp(r[k][1], maxf), scale, 0);
+                    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(r[k][2], maxf), mx_clamp(r[k][3], maxf), scale, 1);
+                    if constexpr (N == 8) {
+                        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(r[k][4], maxf), mx_clamp(r[k][5], maxf), scale, 2);
+                        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(r[k][6], maxf), mx_clamp(r[k][7], maxf), scale, 3);
+                    }
+                } else {
+                    const float inv = mx_inv_scale(byte);
+#pragma unroll
+                    for (int e = 0; e < N; ++e) w |= mx_quant(mx_clamp(r[k][e], maxf), inv) << (4 * e);
+                }
+                mx_residual<T, HW, N>(r[k], &w, byte, maxf);
+            } else {  // a NaN block: the state is reset
+#pragma unroll
+                for (int e = 0; e < N; ++e) r[k][e] = 0.0f;
+            }
+            if constexpr (N == 4) reinterpret_cast<uint16_t*>(pay + b * kMxBlockBytes)[sub] = (uint16_t)w;
+            else reinterpret_cast<uint32_t*>(pay + b * kMxBlockBytes)[sub] = w;
+            if (sub == 0) {
+                seg[b] = (uint8_t)byte;
+                if (b == nb - 1) {  // slack of both regions, zero
+                    for (int64_t q = nb; q < sbytes; ++q) seg[q] = 0;
+                    if (nb * kMxBlockBytes < pbytes)
+                        *reinterpret_cast<uint4*>(pay + nb * kMxBlockBytes) = make_uint4(0u, 0u, 0u, 0u);
+                }
+            }
+            const int64_t j0 = (b0 + k * BW) * kMxBlock + lane * N;
+            if (vecr && full) {
+#pragma unroll
+                for (int h = 0; h < N / 4; ++h) {
+                    const uint4 u = make_uint4(__float_as_uint(r[k][4 * h]), __float_as_uint(r[k][4 * h + 1]),
+                                               __float_as_uint(r[k][4 * h + 2]), __float_as_uint(r[k][4 * h + 3]));
+                    if constexpr (NT) nt_store16(u, rsd + j0 + 4 * h);
+                    else *reinterpret_cast<uint4*>(rsd + j0 + 4 * h) = u;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < N; ++e)
+                    if (j0 + e < cs) rsd[j0 + e] = r[k][e];
+            }
+        }
+    }
+}
+
+// Server step: mxfp4_reduce_encode_kernel (never storing the reduced chunk) with the server
+// residual of the lane's block, 32 f32 read and written as eight 16-B vectors; a residual
+// that is only 4-B aligned and the ragged last block take element accesses.
+template <typename T, int BY, bool HW>
+__global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_ef_kernel(const uint8_t* __restrict__ in, int64_t cs,
+                                                                       int p, int average, float* __restrict__ res,
+                                                                       uint8_t* __restrict__ out_seg) {
+    const int64_t nb = mx_blocks(cs), sbytes = mx_scale_bytes(cs), pbytes = mx_payload_bytes(cs);
+    const int64_t segb = sbytes + pbytes;
+    uint8_t* pay_out = out_seg + sbytes;
+    const bool vec = ((uintptr_t)res % 16) == 0;
+    const float pf = (float)p, maxf = T::init_max();
+    for (int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; b < nb; b += (int64_t)gridDim.x * kBlock) {
+        float x[kMxBlock];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float s[8][BY];
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+#pragma unroll
+                for (int y = 0; y < BY; ++y) s[e][y] = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {  // p <= 2 * BY
+                uint32_t w[BY], sb[BY];
+#pragma unroll
+                for (int y = 0; y < BY; ++y) {
+                    const int cc = r * BY + y < p ? r * BY + y : p - 1;
+                    const uint8_t* seg = in + (int64_t)cc * segb;
+                    sb[y] = seg[b];
+                    w[y] = reinterpret_cast<const uint32_t*>(seg + sbytes + b * kMxBlockBytes)[q];
+                }
+#pragma unroll
+                for (int y = 0; y < BY; ++y) {
+                    if (r * BY + y >= p) break;
+                    uint32_t u[8];
+                    mx_decode<T, HW, 4>(w[y], sb[y], u);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) s[e][y] = s[e][y] + from_stored_bits<T>(u[e]);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                tree_finish<BY>(s[e]);
+                const int64_t j = b * kMxBlock + q * 8 + e;
+                x[q * 8 + e] = j < cs ? as_stored<T>(average ? s[e][0] / pf : s[e][0]) : 0.0f;
+            }
+        }
+        const bool whole = vec && (b + 1) * kMxBlock <= cs;
+        float* rb = res + b * kMxBlock;
+        if (whole) {
+#pragma unroll
+            for (int k = 0; k < kMxBlock / 4; ++k) {
+                const uint4 u = *reinterpret_cast<const uint4*>(rb + 4 * k);
+                x[4 * k] = mx_ef_sum(x[4 * k], __uint_as_float(u.x));
+                x[4 * k + 1] = mx_ef_sum(x[4 * k + 1], __uint_as_float(u.y));
+                x[4 * k + 2] = mx_ef_sum(x[4 * k + 2], __uint_as_float(u.z));
+                x[4 * k + 3] = mx_ef_sum(x[4 * k + 3], __uint_as_float(u.w));
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < kMxBlock; ++e)
+                x[e] = mx_ef_sum(x[e], b * kMxBlock + e < cs ? rb[e] : 0.0f);
+        }
+        uint32_t byte, w[4];
+        mx_encode<HW>(x, maxf, byte, w);
+        out_seg[b] = (uint8_t)byte;
+        *reinterpret_cast<uint4*>(pay_out + b * kMxBlockBytes) = make_uint4(w[0], w[1], w[2], w[3]);
+        if (b == nb - 1) {
+            for (int64_t k = nb; k < sbytes; ++k) out_seg[k] = 0;
+            if (nb * kMxBlockBytes < pbytes)
+                *reinterpret_cast<uint4*>(pay_out + nb * kMxBlockBytes) = make_uint4(0u, 0u, 0u, 0u);
+        }
+        if (byte != kMxNanScale) {
+            mx_residual<T, HW, kMxBlock>(x, w, byte, maxf);
+        } else {
+#pragma unroll
+            for (int e = 0; e < kMxBlock; ++e) x[e] = 0.0f;
+        }
+        if (whole) {
+#pragma unroll
+            for (int k = 0; k < kMxBlock / 4; ++k)
+                *reinterpret_cast<uint4*>(rb + 4 * k) =
+                    make_uint4(__float_as_uint(x[4 * k]), __float_as_uint(x[4 * k + 1]), __float_as_uint(x[4 * k + 2]),
+                               __float_as_uint(x[4 * k + 3]));
+        } else {
+#pragma unroll
+            for (int e = 0; e < kMxBlock; ++e)
+                if (b * kMxBlock + e < cs) rb[e] = x[e];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------
 // BAGUA_MXFP4_HWCVT=1 (the default) / 0: the hardware conversions or the arithmetic (A/B; same bytes)
@@ -416,11 +675,122 @@ static int mx_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, int
     return check_launch();
 }
 
+// ---- error feedback ----
+template <typename T, bool HW>
+static void mx_launch_encode_ef(const dim3& grid, bool nt, const typename T::storage* in, int64_t cs, float* res,
+                                uint8_t* out, hipStream_t s) {
+    if (nt) launch(mxfp4_encode_ef_kernel<T, HW, true>, grid, dim3(kBlock), 0, s, in, cs, res, out);
+    else launch(mxfp4_encode_ef_kernel<T, HW, false>, grid, dim3(kBlock), 0, s, in, cs, res, out);
+}
+
+template <typename T>
+static int mx_compress_ef_impl(const void* input, int in_num_elem, int cs, int p, uint8_t* out, size_t out_bytes,
+                               int target, float* residual, hipStream_t s) {
+    using S = typename T::storage;
+    if (p <= 0 || p > 65535 || cs < 0 || target != -1 || !out || !input) return BAGUA_ERR_INVALID_ARG;
+    if ((int64_t)in_num_elem != (int64_t)cs * p) return BAGUA_ERR_INVALID_ARG;  // every chunk fully valid
+    if (!residual || (uintptr_t)residual % 4) return BAGUA_ERR_INVALID_ARG;
+    if (out_bytes < (size_t)p * (size_t)mx_segment_bytes(cs)) return BAGUA_ERR_INVALID_ARG;
+    if ((uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;
+    if (cs == 0) return BAGUA_OK;
+    constexpr int64_t kTileElems = kMxItemBytes * kWave / (int64_t)sizeof(S);
+    const dim3 grid(mx_grid(((int64_t)cs + kTileElems - 1) / kTileElems, kWavesPerBlock, p, "BAGUA_TUNE_MX_ENCODE_BLOCKS"),
+                    p);
+    // Residual policy by what the step streams, gradient plus residual: up to the 256 MiB
+    // Infinity Cache default-policy accesses (the next step's encode may find the residual
+    // there; not measured), past it non-temporal ones.  For 256 MiB of f32 non-temporal took
+    // 143 against 146 us and the decode behind it 47 against 63 us; for 2^27 bf16 276 against
+    // 252 us and the decode 56 against 62 us, so there the default policy was ahead in sum
+    // (profiles/r09_mxfp4_ef.json; MXFP4.md).
+    // BAGUA_MX_EF_RESIDUAL_NT=1 / 0 forces either (A/B).
+    const int env = tune_int("BAGUA_MX_EF_RESIDUAL_NT", -1);
+    const bool nt = env >= 0 ? env != 0 : (int64_t)cs * p * (4 + (int64_t)sizeof(S)) > ((int64_t)256 << 20);
+    if (mx_hw()) mx_launch_encode_ef<T, true>(grid, nt, static_cast<const S*>(input), (int64_t)cs, residual, out, s);
+    else mx_launch_encode_ef<T, false>(grid, nt, static_cast<const S*>(input), (int64_t)cs, residual, out, s);
+    return check_launch();
+}
+
+template <typename T, bool HW>
+static void mx_dispatch_reduce_ef(int blocks, const uint8_t* in, int64_t cs, int p, int average, float* res,
+                                  uint8_t* seg, hipStream_t s) {
+    switch (reduce_by(p)) {
+        case 2:
+            launch(mxfp4_reduce_encode_ef_kernel<T, 2, HW>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average, res, seg);
+            break;
+        case 4:
+            launch(mxfp4_reduce_encode_ef_kernel<T, 4, HW>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average, res, seg);
+            break;
+        default:
+            launch(mxfp4_reduce_encode_ef_kernel<T, 8, HW>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average, res, seg);
+            break;
+    }
+}
+
+template <typename T>
+static int mx_reduce_requantize_ef_impl(const uint8_t* recv, size_t recv_bytes, int cs, int p, int average,
+                                        uint8_t* out, size_t out_bytes, int target, float* residual, hipStream_t s) {
+    if (p <= 0 || cs < 0 || target < 0 || target >= p || !recv || !out) return BAGUA_ERR_INVALID_ARG;
+    if (!residual || (uintptr_t)residual % 4) return BAGUA_ERR_INVALID_ARG;
+    if (p > kMaxFusedChunks) return BAGUA_ERR_UNSUPPORTED;  // caller runs decompress + reduce + compress_ef
+    const size_t segb = (size_t)mx_segment_bytes(cs);
+    if (recv_bytes < (size_t)p * segb || out_bytes < (size_t)p * segb) return BAGUA_ERR_INVALID_ARG;
+    if ((uintptr_t)recv % 4 || (uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;
+    if (cs == 0) return BAGUA_OK;
+    uint8_t* seg = out + (size_t)target * segb;
+    const int blocks = mx_grid(mx_blocks(cs), kBlock, 1, "BAGUA_TUNE_MX_MIDDLE_BLOCKS");
+    if (mx_hw()) mx_dispatch_reduce_ef<T, true>(blocks, recv, (int64_t)cs, p, average, residual, seg, s);
+    else mx_dispatch_reduce_ef<T, false>(blocks, recv, (int64_t)cs, p, average, residual, seg, s);
+    return check_launch();
+}
+
 }  // namespace bagua
 
 using namespace bagua;
 
 extern "C" {
+
+int bagua_mxfp4_ef_state_bytes(int chunk_size, int num_chunks, size_t* worker_bytes, size_t* server_bytes) {
+    if (chunk_size < 0 || num_chunks <= 0 || !worker_bytes || !server_bytes) return BAGUA_ERR_INVALID_ARG;
+    *worker_bytes = (size_t)chunk_size * (size_t)num_chunks * sizeof(float);
+    *server_bytes = (size_t)chunk_size * sizeof(float);
+    return BAGUA_OK;
+}
+
+int bagua_mxfp4_compress_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                            uint8_t* output, size_t output_bytes, int target_chunk, float* residual,
+                            bagua_stream_t stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case BAGUA_DTYPE_F32:
+            return mx_compress_ef_impl<F32>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
+                                            target_chunk, residual, s);
+        case BAGUA_DTYPE_F16:
+            return mx_compress_ef_impl<F16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
+                                            target_chunk, residual, s);
+        case BAGUA_DTYPE_BF16:
+            return mx_compress_ef_impl<BF16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
+                                             target_chunk, residual, s);
+    }
+    return BAGUA_ERR_UNSUPPORTED;
+}
+
+int bagua_mxfp4_reduce_requantize_ef(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                     int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                     int target_chunk, float* residual, bagua_stream_t stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+        case BAGUA_DTYPE_F32:
+            return mx_reduce_requantize_ef_impl<F32>(input, input_bytes, chunk_size, num_chunks, average, output,
+                                                     output_bytes, target_chunk, residual, s);
+        case BAGUA_DTYPE_F16:
+            return mx_reduce_requantize_ef_impl<F16>(input, input_bytes, chunk_size, num_chunks, average, output,
+                                                     output_bytes, target_chunk, residual, s);
+        case BAGUA_DTYPE_BF16:
+            return mx_reduce_requantize_ef_impl<BF16>(input, input_bytes, chunk_size, num_chunks, average, output,
+                                                      output_bytes, target_chunk, residual, s);
+    }
+    return BAGUA_ERR_UNSUPPORTED;
+}
 
 size_t bagua_mxfp4_compressed_bytes(int chunk_size, int num_chunks) {
     if (chunk_size < 0 || num_chunks < 0) return 0;

@@ -95,4 +95,54 @@ MX_HD void mx_encode_block(const float (&x)[kMxBlock], float maxf, uint32_t& byt
     for (int e = 0; e < kMxBlock; ++e) w[e / 8] |= mx_quant(mx_clamp(x[e], maxf), inv) << (4 * (e % 8));
 }
 
+// ---- error feedback (MXFP4.md, "Error feedback") -----------------------------------
+// K: 0 f32, 1 f16, 2 bf16 (the BAGUA_DTYPE_* codes).
+
+// A decoded value d (finite, |d| <= the largest finite T) as it reads back after a store
+// to T, round to nearest even.  bf16 is the upper half of the f32 bits, denormals included.
+// A decode in f16's normal range is exact (a 2-bit significand); below 2^-14 f16's step is
+// 2^-24, and adding 0.5, whose unit in the last place is 2^-24, rounds |d| to it in the add.
+template <int K>
+MX_HD float mx_as_stored(float d) {
+    if constexpr (K == 2) {
+        const uint32_t u = mx_bits(d);
+        return mx_float((u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u);
+    } else if constexpr (K == 1) {
+        const uint32_t u = mx_bits(d), a = u & 0x7fffffffu;
+        if (a >= 0x38800000u) return d;  // |d| >= 2^-14
+        const float r = (mx_float(a) + 0.5f) - 0.5f;
+        return mx_float(mx_bits(r) | (u & 0x80000000u));
+    } else {
+        return d;
+    }
+}
+
+// the compensated value of the rule: x + e, one binary32 add (a NaN stays a NaN)
+MX_HD float mx_ef_sum(float x, float e) { return x + e; }
+
+// the new residual of one element of a block that holds no NaN: vc = the clamped
+// compensated value, d = the decode of its nibble (mx_dequant: clamped f32)
+template <int K>
+MX_HD float mx_ef_residual(float vc, float d) { return vc - mx_as_stored<K>(d); }
+
+// One block of the rule: x[32] as f32 and the residual e[32] -> scale byte, payload words
+// and the new residual (all +0 for a NaN block: the state is reset, not poisoned).
+template <int K>
+MX_HD void mx_encode_block_ef(const float (&x)[kMxBlock], float (&e)[kMxBlock], float maxf, uint32_t& byte,
+                              uint32_t (&w)[4]) {
+    float v[kMxBlock];
+#pragma unroll
+    for (int i = 0; i < kMxBlock; ++i) v[i] = mx_ef_sum(x[i], e[i]);
+    mx_encode_block(v, maxf, byte, w);
+    if (byte == kMxNanScale) {
+#pragma unroll
+        for (int i = 0; i < kMxBlock; ++i) e[i] = 0.0f;
+        return;
+    }
+    const float hs = mx_half_scale(byte);
+#pragma unroll
+    for (int i = 0; i < kMxBlock; ++i)
+        e[i] = mx_ef_residual<K>(mx_clamp(v[i], maxf), mx_dequant((w[i / 8] >> (4 * (i % 8))) & 15u, hs, maxf));
+}
+
 }  // namespace bagua

@@ -161,6 +161,9 @@ int run_op(const bagua_bucket_op_t& op, const bagua_tensor_t* flat, const char* 
             return bagua_centralized_onebit_error_feedback(op.comm, flat, op.average, &op.ef_worker_carry,
                                                            &op.ef_worker_scales, &op.ef_server_carry,
                                                            &op.ef_server_scale, 0);
+        case BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK:
+            return bagua_centralized_mxfp4_error_feedback(op.comm, flat, op.average, &op.ef_worker_carry,
+                                                          &op.ef_server_carry);
         case BAGUA_BUCKET_OP_CALLBACK:
             // the callback sees the previous ops' results, as in the reference (their
             // Drop synced), also when the worker runs the ops async
@@ -624,8 +627,15 @@ int bagua_bucket_append_op(BaguaBucketC* b, const bagua_bucket_op_t* op) {
     if (op->kind != BAGUA_BUCKET_OP_CALLBACK && !op->comm && !op->intranode) return BAGUA_ERR_INVALID_ARG;
     if (op->intranode && op->intranode->rank == 0 && !op->comm) return BAGUA_ERR_INVALID_ARG;
     if (op->kind < BAGUA_BUCKET_OP_CENTRALIZED_LOW_PRECISION ||
-        op->kind > BAGUA_BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK)
+        op->kind > BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK)
         return BAGUA_ERR_UNSUPPORTED;
+    if (op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK) {
+        // MXFP4 codec only, no hierarchical mode, both residuals present, no scale tensors
+        if (op->intranode || op->compression != BAGUA_COMPRESSION_MXFP4) return BAGUA_ERR_UNSUPPORTED;
+        if (!op->ef_worker_carry.ptr || !op->ef_server_carry.ptr || op->ef_worker_scales.ptr ||
+            op->ef_server_scale.ptr)
+            return BAGUA_ERR_INVALID_ARG;
+    }
     if (op->kind == BAGUA_BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK) {
         // 1-bit codec only, no hierarchical mode, all four state tensors present
         if (op->intranode || op->compression != BAGUA_COMPRESSION_ONEBIT) return BAGUA_ERR_UNSUPPORTED;

@@ -152,7 +152,7 @@ int env_int(const char* name, long dflt);
 int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_tensor_t* t, uint64_t chunk,
                    int sched, int average);
 enum { kOpCentralized = 1, kOpCentralizedUnfused, kOpCentralizedPipelined, kOpOneBitPipelined, kOpRing,
-       kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback };
+       kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback };
 
 int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int method, bool fused) {
     OpTimer tm;
@@ -827,6 +827,60 @@ int centralized_onebit_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
     return finish_both(c, BAGUA_OK);
 }
 
+// The MXFP4 op with error feedback (MXFP4.md): centralized()'s steps for the MXFP4 codec
+// with the two `_ef` kernels.  The worker residual compensates what this rank encodes for
+// the alltoall, the server residual the own chunk it re-encodes for the allgather; wire
+// format, collectives, segment sizes and the final decode are the plain op's.  One stream,
+// no pieces; one rank takes the same path (its own bytes arrive by a device copy).
+int centralized_mxfp4_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, float* worker,
+                         float* server) {
+    Chunking k;
+    int rc = plan(c, t, BAGUA_COMPRESSION_MXFP4, &k);
+    if (rc) return rc;
+    if (t->ptr % 16)
+        return with_aligned_copy(c, {t}, [&](const std::vector<const bagua_tensor_t*>& u) {
+            return centralized_mxfp4_ef(c, u[0], average, worker, server);
+        });
+    DeviceGuard guard(c->device_id);
+    if ((rc = check_schedule(c, kOpMxfp4ErrorFeedback, BAGUA_COMPRESSION_MXFP4, t, k.cs, 1, average))) return rc;
+    const uint64_t s = (uint64_t)(uintptr_t)c->stream;
+    void* sp = (void*)(uintptr_t)s;
+    const int dt = t->dtype, cs = (int)k.cs, p = k.p;
+    OpBuffer send(c), recv(c);
+    TRY(send.allocate(c->device_id, k.S));
+    TRY(recv.allocate(c->device_id, k.S));
+    const bagua_tensor_t sv = u8_view(send.ptr(), k.S, c->device_id);
+    const bagua_tensor_t rv = u8_view(recv.ptr(), k.S, c->device_id);
+    // 1. compensate + encode every chunk (worker residual in place)
+    TRY(bagua_mxfp4_compress_ef(dt, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, cs, p, send.as<uint8_t>(), k.S, -1,
+                                worker, sp));
+    // 2. alltoall: slot j of recv <- rank j's segment `rank`
+    if (p == 1)
+        TRY(hipMemcpyAsync(recv.as<void>(), send.as<void>(), k.S, hipMemcpyDeviceToDevice, c->stream) == hipSuccess
+                ? BAGUA_OK
+                : BAGUA_ERR_HIP);
+    else
+        TRY(c->t->alltoall(send.as<void>(), recv.as<void>(), k.S / k.p, BAGUA_DTYPE_U8, c->stream));
+    // 3. decode the p received versions of the own chunk, reduce, compensate with the server
+    // residual, re-encode into send[rank] (the reduced chunk is not stored)
+    rc = bagua_mxfp4_reduce_requantize_ef(dt, recv.as<uint8_t>(), k.S, cs, p, average, send.as<uint8_t>(), k.S, k.rank,
+                                          server, sp);
+    if (rc == BAGUA_ERR_UNSUPPORTED) {
+        // more chunks than the fused kernel takes: decode + reduce into the tensor, then the
+        // worker encode on the own chunk alone (one chunk, into its segment)
+        const size_t co = k.S / k.p;
+        TRY(bagua_tensor_decompress_from(t, BAGUA_COMPRESSION_MXFP4, p, &rv, s));
+        TRY(bagua_tensor_reduce_inplace(t, p, k.rank, average, s));
+        rc = bagua_mxfp4_compress_ef(dt, (const uint8_t*)(uintptr_t)t->ptr + (size_t)k.rank * k.cs * bagua_dtype_bytes(dt),
+                                     cs, cs, 1, send.as<uint8_t>() + (size_t)k.rank * co, co, -1, server, sp);
+    }
+    TRY(rc);
+    // 4. allgather the requantised chunks in place, 5. decode everything
+    if (p > 1) TRY(bagua_comm_allgather_inplace(c, &sv));
+    TRY(bagua_tensor_decompress_from(t, BAGUA_COMPRESSION_MXFP4, p, &sv, s));
+    return finish(c, BAGUA_OK);
+}
+
 // ---- ring exchange schedule ------------------------------------------------
 // The reference sends the whole compressed bucket straight to both ring peers
 // (decentralized_low_precision_synchronous.rs:98-115).  On a fully connected
@@ -1029,6 +1083,24 @@ int bagua_centralized_onebit_error_feedback(BaguaSingleCommunicatorC* c, const b
         (rc = ef_tensor(server_scale, 1, t->device_id, &st.ss)))
         return rc;
     return centralized_onebit_ef(c, t, average, st, pieces);
+}
+
+int bagua_centralized_mxfp4_error_feedback(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
+                                           const bagua_tensor_t* worker_residual,
+                                           const bagua_tensor_t* server_residual) {
+    // every refusal before anything is launched or posted
+    if (!c || !c->t || !t || !t->ptr) return BAGUA_ERR_INVALID_ARG;
+    if (!is_float_dtype(t->dtype)) return BAGUA_ERR_UNSUPPORTED;
+    if (t->num_elem != t->num_elem_allocated) return BAGUA_ERR_UNSUPPORTED;  // partly valid tensors: the plain op only
+    const uint64_t p = c->nranks;
+    if (!t->num_elem || t->num_elem % p || t->num_elem > 0x7fffffffULL || t->device_id != (int)c->device_id)
+        return BAGUA_ERR_INVALID_ARG;
+    float *worker = nullptr, *server = nullptr;
+    int rc;
+    if ((rc = ef_tensor(worker_residual, t->num_elem, t->device_id, &worker)) ||
+        (rc = ef_tensor(server_residual, t->num_elem / p, t->device_id, &server)))
+        return rc;
+    return centralized_mxfp4_ef(c, t, average, worker, server);
 }
 
 int bagua_centralized_low_precision_synchronous(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,

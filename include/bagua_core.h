@@ -97,6 +97,11 @@ int bagua_tensor_compress_into(const bagua_tensor_t* t, int method, int n_chunks
 int bagua_tensor_compress_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
                                          const bagua_tensor_t* carry, const bagua_tensor_t* scales,
                                          bagua_tensor_t* out);
+/* bagua_tensor_compress with the "MXFP4" codec and error-feedback state
+ * (bagua_mxfp4_compress_ef): `residual` (t->num_elem F32) on the tensor's device, 16-B
+ * aligned, updated in place on `stream`; every chunk compressed. */
+int bagua_tensor_compress_mxfp4_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
+                                               const bagua_tensor_t* residual, bagua_tensor_t* out);
 /* RawBaguaTensor::decompress_from (datatypes/mod.rs:398-446) */
 int bagua_tensor_decompress_from(const bagua_tensor_t* t, int method, int n_chunks,
                                  const bagua_tensor_t* compressed, uint64_t stream);
@@ -197,6 +202,21 @@ int bagua_centralized_onebit_error_feedback(BaguaSingleCommunicatorC* comm, cons
                                             const bagua_tensor_t* worker_carry, const bagua_tensor_t* worker_scales,
                                             const bagua_tensor_t* server_carry, const bagua_tensor_t* server_scale,
                                             int pieces);
+/* The MXFP4 op with error feedback (MXFP4.md): the centralized op with the "MXFP4" codec,
+ * where each rank carries its quantisation error into the next step -- once for what it
+ * encodes for the alltoall (worker_residual, t->num_elem F32) and once for the own chunk it
+ * re-encodes for the allgather (server_residual, t->num_elem / nranks F32).  The state is
+ * the caller's, on the tensor's device, 16-B aligned, zero before the first step.  Wire
+ * format, collectives and segment sizes are the plain op's.  One kernel for the worker
+ * step and one for the middle step up to 16 ranks; past that the middle step is decode +
+ * reduce into the tensor and the worker kernel on the own chunk.  Its own kind under
+ * BAGUA_CHECK_SCHEDULE: a rank running the plain MXFP4 op against it is a schedule
+ * mismatch.  Refused before anything is launched: num_elem < num_elem_allocated and
+ * non-float dtypes (BAGUA_ERR_UNSUPPORTED), state of the wrong size, dtype, device or
+ * alignment (BAGUA_ERR_INVALID_ARG); there is no hierarchical and no pieced form. */
+int bagua_centralized_mxfp4_error_feedback(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t, int average,
+                                           const bagua_tensor_t* worker_residual,
+                                           const bagua_tensor_t* server_residual);
 /* the reference's unfused sequence, kept for A/B measurement and parity */
 int bagua_centralized_low_precision_synchronous_unfused(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t,
                                                         int average, int method);
@@ -275,7 +295,8 @@ enum {
     BAGUA_BUCKET_OP_CENTRALIZED_FULL_PRECISION = 2,  /* centralized_full_precision_synchronous.rs */
     BAGUA_BUCKET_OP_DECENTRALIZED_LOW_PRECISION = 3, /* decentralized_low_precision_synchronous.rs */
     BAGUA_BUCKET_OP_CALLBACK = 4,                    /* python_ffi_op.rs: callback(user, bucket name) */
-    BAGUA_BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK = 5 /* bagua_centralized_onebit_error_feedback */
+    BAGUA_BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK = 5, /* bagua_centralized_onebit_error_feedback */
+    BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK = 6   /* bagua_centralized_mxfp4_error_feedback */
 };
 
 typedef struct bagua_bucket_op {
@@ -292,7 +313,9 @@ typedef struct bagua_bucket_op {
     BaguaSingleCommunicatorC* intranode;
     /* BAGUA_BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK: the op's state (F32, on the bucket's
      * device, sized for the flattened bucket; see bagua_centralized_onebit_error_feedback).
-     * Zeroed = absent, so initialisers written before these fields existed mean what they meant. */
+     * Zeroed = absent, so initialisers written before these fields existed mean what they meant.
+     * BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK: its two residuals travel in
+     * ef_worker_carry and ef_server_carry; the two scale fields must be absent. */
     bagua_tensor_t ef_worker_carry, ef_worker_scales, ef_server_carry, ef_server_scale;
 } bagua_bucket_op_t;
 

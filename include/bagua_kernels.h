@@ -238,6 +238,31 @@ int bagua_mxfp4_reduce_requantize(int dtype, const uint8_t* input, size_t input_
                                   void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
                                   bagua_stream_t stream);
 
+/* MXFP4 with error feedback (MXFP4.md, "Error feedback"): the same wire format, plus
+ * caller-owned f32 state, zero before the first step, that carries each step's
+ * quantisation error into the next.  The state is the residual itself: worker
+ * residual[chunk_size * num_chunks], server residual[chunk_size].  Per element, in binary32:
+ * v = x + residual, clamped to the largest finite T unless NaN; the block is the plain
+ * encode of the 32 clamped v; residual = clamped v - its decode as stored in T, and +0 for
+ * every element of a NaN block.  Every chunk must be fully valid (input_num_element ==
+ * chunk_size * num_chunks).  BAGUA_ERR_INVALID_ARG: a null residual or one that is not
+ * 4-B aligned (16-B alignment of each chunk's part takes the vector path), a partly valid
+ * input, a short buffer, a misaligned output; BAGUA_ERR_UNSUPPORTED: dtypes other than
+ * F32 / F16 / BF16.  Nothing is launched on a refusal.  One kernel each, no workspace. */
+int bagua_mxfp4_ef_state_bytes(int chunk_size, int num_chunks, size_t* worker_bytes, size_t* server_bytes);
+/* bagua_mxfp4_compress's arguments plus the state; target_chunk = -1 only. */
+int bagua_mxfp4_compress_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                            uint8_t* output, size_t output_bytes, int target_chunk, float* residual,
+                            bagua_stream_t stream);
+/* bagua_mxfp4_reduce_requantize with the server state: the reduced value of element j of
+ * chunk `target_chunk`, as stored in T, is the x of the rule (residual[j]); the reduced
+ * chunk is never stored.  BAGUA_ERR_UNSUPPORTED for num_chunks > 16: callers then run
+ * bagua_mxfp4_decompress + bagua_reduce_chunks and bagua_mxfp4_compress_ef on the own chunk
+ * (one chunk, into its segment). */
+int bagua_mxfp4_reduce_requantize_ef(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                     int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                     int target_chunk, float* residual, bagua_stream_t stream);
+
 /* ======================================================================== */
 /* v2 — chunk reduction and elementwise ops                                  */
 /* ======================================================================== */
