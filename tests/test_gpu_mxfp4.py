@@ -228,13 +228,15 @@ def received(rng, p, cs, dtype):
         return R.compress(NP.from_f32(x, dtype), dtype, p)
 
 
-@pytest.mark.parametrize("p", [1, 2, 3, 4, 8, 16])
+@pytest.mark.parametrize("p", list(range(1, 17)))
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_reduce_requantize(bc, dtype, p, monkeypatch):
+    """every p the fused middle step takes: for p = 5 to 7 and 9 to 15 the summation tree's second round
+    is partly filled (the kernel breaks out of it at p and clamps the index it loads from)"""
     K = bc._native.K
     monkeypatch.setenv("BAGUA_TUNE_MX_MIDDLE_BLOCKS", "2")  # cs below spans two grid-stride iterations
     rng = np.random.default_rng(100 * dtype + p)
-    for cs in (1000, 2 * 8192 + 33):
+    for cs in (1000, 2 * 8192 + 33) if p in (1, 2, 3, 4, 8, 16) else (1000,):
         recv = received(rng, p, cs, dtype)
         S = recv.size
         rt = torch.from_numpy(recv).cuda()
