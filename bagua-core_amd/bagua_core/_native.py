@@ -146,6 +146,9 @@ KERNEL_SIGNATURES = {
     "bagua_mxfp4_ef_state_bytes": (_i32, [_i32, _i32, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
     "bagua_mxfp4_compress_ef": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
     "bagua_mxfp4_reduce_requantize_ef": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
+    "bagua_ring_mix_mxfp4": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "bagua_ring_apply_mxfp4": (_i32, [_i32, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "bagua_ring_one_rank_mxfp4": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "bagua_reduce_chunks": (_i32, [_i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "bagua_add_inplace": (_i32, [_i32, _vp, _vp, _i32, _vp]),
     "bagua_addmul_inplace": (_i32, [_i32, _vp, _vp, _i32, _f32, _vp]),

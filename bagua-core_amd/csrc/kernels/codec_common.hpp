@@ -34,6 +34,7 @@ struct F32 {
     __device__ static __forceinline__ float load(const storage* p, int64_t i) { return p[i]; }
     __device__ static __forceinline__ float to_f(storage v) { return v; }
     __device__ static __forceinline__ storage from_f(float v) { return v; }
+    __device__ static __forceinline__ float stored(float v) { return v; }
     // K:306/359/369 (f16) and cub Traits<float>::Max (f32): reduction init
     __device__ static __forceinline__ float init_max() { return __int_as_float(0x7f7fffff); }
 };
@@ -48,6 +49,7 @@ struct F16 {
     __device__ static __forceinline__ storage from_f(float v) {  // __float2half: RNE
         return __builtin_bit_cast(uint16_t, (_Float16)v);
     }
+    __device__ static __forceinline__ float stored(float v) { return to_f(from_f(v)); }
     __device__ static __forceinline__ float init_max() { return 65504.0f; }
 };
 
@@ -61,6 +63,7 @@ struct BF16 {
     __device__ static __forceinline__ storage from_f(float v) {  // RNE (v_cvt_pk_bf16_f32)
         return __builtin_bit_cast(uint16_t, (__bf16)v);
     }
+    __device__ static __forceinline__ float stored(float v) { return to_f(from_f(v)); }
     __device__ static __forceinline__ float init_max() { return __uint_as_float(0x7f7f0000u); }
 };
 
@@ -68,8 +71,7 @@ struct BF16 {
 // reference materialises every decompressed value in a T tensor first
 template <typename T>
 __device__ __forceinline__ float as_stored(float f) {
-    if constexpr (sizeof(typename T::storage) == 4) return f;
-    else return T::to_f(T::from_f(f));
+    return T::stored(f);
 }
 
 // ------------------------------------------------------ order-free min/max --

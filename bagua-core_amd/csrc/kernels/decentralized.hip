@@ -22,6 +22,7 @@
 // (ring_one_rank_kernel, bagua_ring_one_rank_minmax).
 #include "codec_common.hpp"
 #include "launch_util.hpp"
+#include "ring_mix.hpp"
 
 #include <type_traits>
 
@@ -76,22 +77,7 @@ static int apply_cfg() {
     return c >= 0 && c < kApplyNumCfg ? c : kApplyDefaultCfg;
 }
 
-// K:236-244 addmul as the elementwise kernels compute it (elementwise.hip)
-template <typename T>
-__device__ __forceinline__ float addmul(float x, float y, float f) {
-    if constexpr (sizeof(typename T::storage) == 4) return __builtin_fmaf(y, f, x);
-    else return as_stored<T>(x + as_stored<T>(y * f));
-}
-
-// addmul<T> already returns a value rounded to T (the 16-bit path ends in
-// as_stored; f32 is stored as computed), and rounding is idempotent, so no
-// further rounding is applied between the steps
-template <typename T>
-__device__ __forceinline__ float mix(float t, float l, float r, float w, float f13, float f53) {
-    t = addmul<T>(t, l, f13);
-    t = addmul<T>(t, r, f13);
-    return addmul<T>(t, w, f53);
-}
+// addmul<T> and mix<T>, the three rounded steps of :45-60: ring_mix.hpp
 
 // STORE = false: the min/max partials of the mixed values only, t untouched (the
 // one-rank op's first pass; its second pass recomputes the mix, ring_one_rank_kernel).

@@ -23,18 +23,12 @@
 #include "codec_common.hpp"
 #include "launch_util.hpp"
 #include "mxfp4_common.hpp"
+#include "mxfp4_device.hpp"
 
 namespace bagua {
 
 constexpr int kMxItemBytes = 128;  // input bytes a lane of the encode has in flight per iteration
 constexpr int kMxDecodeVecs = 4;   // 16-B output vectors per lane per decode iteration
-
-template <typename T>
-__device__ __forceinline__ uint32_t mx_nan_bits() {  // canonical quiet NaN of T
-    if constexpr (sizeof(typename T::storage) == 4) return 0x7fc00000u;
-    else if constexpr (T::kDtype == BAGUA_DTYPE_F16) return 0x7e00u;
-    else return 0x7fc0u;
-}
 
 __device__ __forceinline__ int64_t mx_valid(int64_t in_num_elem, int64_t cs, int c) {
     const int64_t r = in_num_elem - (int64_t)c * cs;
@@ -64,36 +58,6 @@ __device__ __forceinline__ void mx_encode(const float (&x)[kMxBlock], float maxf
             w[k] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w[k], mx_clamp(x[8 * k + 4], maxf), mx_clamp(x[8 * k + 5], maxf), scale, 2);
             w[k] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w[k], mx_clamp(x[8 * k + 6], maxf), mx_clamp(x[8 * k + 7], maxf), scale, 3);
         }
-    }
-}
-
-// NB payload bytes (word w, low byte first) of a block with scale byte sb -> 2 * NB values
-// as T stores them (bits; 16-bit patterns zero-extended)
-template <typename T, bool HW, int NB>
-__device__ __forceinline__ void mx_decode(uint32_t w, uint32_t sb, uint32_t (&u)[2 * NB]) {
-    if (sb == kMxNanScale) {
-#pragma unroll
-        for (int e = 0; e < 2 * NB; ++e) u[e] = mx_nan_bits<T>();
-        return;
-    }
-    const float maxf = T::init_max();
-    if constexpr (HW) {
-        typedef float f32x2v __attribute__((ext_vector_type(2)));
-        const float scale = __uint_as_float(sb << 23);
-        f32x2v r[NB];
-        r[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 0);
-        if constexpr (NB > 1) r[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 1);
-        if constexpr (NB > 2) r[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 2);
-        if constexpr (NB > 3) r[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 3);
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            u[2 * k] = stored_bits<T>(mx_clamp(r[k].x, maxf));
-            u[2 * k + 1] = stored_bits<T>(mx_clamp(r[k].y, maxf));
-        }
-    } else {
-        const float hs = mx_half_scale(sb);
-#pragma unroll
-        for (int e = 0; e < 2 * NB; ++e) u[e] = stored_bits<T>(mx_dequant((w >> (4 * e)) & 15u, hs, maxf));
     }
 }
 
@@ -578,15 +542,7 @@ __global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_ef_kernel(const ui
 // ------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------
-// BAGUA_MXFP4_HWCVT=1 (the default) / 0: the hardware conversions or the arithmetic (A/B; same bytes)
-static bool mx_hw() { return tune_int("BAGUA_MXFP4_HWCVT", 1) != 0; }
-
-static int mx_grid(int64_t items, int64_t per_block, int nact, const char* knob) {
-    int64_t b = (items + per_block - 1) / per_block;
-    const int64_t cap = (tune_int(knob, 2 * kTargetBlocks) + nact - 1) / nact;
-    if (b > cap) b = cap;
-    return (int)(b < 1 ? 1 : b);
-}
+// mx_hw() and mx_grid(): mxfp4_device.hpp
 
 template <typename T>
 static int mx_compress_impl(const void* input, int in_num_elem, int cs, int p, uint8_t* out, size_t out_bytes,

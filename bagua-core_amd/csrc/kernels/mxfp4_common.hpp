@@ -145,4 +145,72 @@ MX_HD void mx_encode_block_ef(const float (&x)[kMxBlock], float (&e)[kMxBlock], 
         e[i] = mx_ef_residual<K>(mx_clamp(v[i], maxf), mx_dequant((w[i / 8] >> (4 * (i % 8))) & 15u, hs, maxf));
 }
 
+// ---- the decentralized ring op (MXFP4.md, "Ring op") ---------------------------------
+// Per element, with the block's scale byte between the second and the third line:
+//   m = mix<T>(t, l, r, w, 1/3, -5/3)                      ring_mix.hpp
+//   (byte, nibble) = the plain block encode of the 32 m    mx_encode_block
+//   d = mx_dq<T>(nibble, byte)                             the decode as stored in T
+//   L = stored(L + d_left); R = stored(R + d_right); t = stored(d_mine + W); W = t
+// T is a dtype as in ring_mix.hpp: the kernels pass F32 / F16 / BF16 (codec_common.hpp),
+// the host check MxT<K> below.
+
+// any f32 value as f16 / bf16 bits, round to nearest even, and back: what the device's
+// conversions give (a NaN comes out quiet), in integer and exact binary32 steps
+MX_HD uint32_t mx_f16_bits(float f) {
+    const uint32_t u = mx_bits(f), s = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return s | 0x7e00u | ((a >> 13) & 0x3ffu);
+    if (a >= 0x477ff000u) return s | 0x7c00u;  // 65520 and above round to inf
+    if (a >= 0x38800000u) return s | (((a + 0xfffu + ((a >> 13) & 1u)) >> 13) - (112u << 10));
+    return s | (mx_bits(mx_float(a) + 0.5f) - 0x3f000000u);  // units of 2^-24, rounded in the add
+}
+MX_HD float mx_f16_value(uint32_t h) {
+    const uint32_t s = (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
+    if (e == 31u) return mx_float(s | 0x7f800000u | (m << 13));
+    if (e == 0u) return mx_float(s | mx_bits((float)m * mx_float(0x33800000u)));  // m * 2^-24, exact
+    return mx_float(s | ((e + 112u) << 23) | (m << 13));
+}
+MX_HD uint32_t mx_bf16_bits(float f) {
+    const uint32_t u = mx_bits(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+template <int K>
+struct MxT {  // K: 0 f32, 1 f16, 2 bf16
+    using storage = uint16_t;
+    static MX_HD float to_f(storage v) { return K == 1 ? mx_f16_value(v) : mx_float((uint32_t)v << 16); }
+    static MX_HD storage from_f(float f) { return (storage)(K == 1 ? mx_f16_bits(f) : mx_bf16_bits(f)); }
+    static MX_HD float stored(float f) { return to_f(from_f(f)); }
+};
+template <>
+struct MxT<0> {
+    using storage = float;
+    static MX_HD float to_f(storage v) { return v; }
+    static MX_HD storage from_f(float f) { return f; }
+    static MX_HD float stored(float f) { return f; }
+};
+
+// the mix factors: f64 literals cast to f32, then to T by the 16-bit kernels (K:600)
+inline float mx_ring_factor(int dtype, double f) {
+    const float v = (float)f;
+    return dtype == 1 ? MxT<1>::stored(v) : dtype == 2 ? MxT<2>::stored(v) : v;
+}
+
+// a nibble of a block with scale byte `byte` as the decode stores it in T: the canonical
+// NaN under 0xFF, otherwise the grid value, magnitude clamped to maxf, rounded to T
+template <typename T>
+MX_HD float mx_dq(uint32_t nib, uint32_t byte, float maxf) {
+    if (byte == kMxNanScale) return mx_float(0x7fc00000u);
+    return T::stored(mx_dequant(nib, mx_half_scale(byte), maxf));
+}
+
+// :126-151 with the three decoded values of one element
+template <typename T>
+MX_HD void mx_ring_apply(float d_mine, float d_left, float d_right, float& t, float& w, float& l, float& r) {
+    l = T::stored(l + d_left);   // L += dq(from_left)
+    r = T::stored(r + d_right);  // R += dq(from_right)
+    t = T::stored(d_mine + w);   // t = dq(mine) + W
+    w = t;                       // W = t (clone)
+}
+
 }  // namespace bagua

@@ -1134,11 +1134,15 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
     const int n = (int)t->num_elem_allocated;
     const size_t S = bagua_compressed_size(method, t->dtype, 1, t->num_elem_allocated);
     if (!S) return BAGUA_ERR_UNSUPPORTED;
-    // fused kernels (csrc/kernels/decentralized.hip) for fully valid, same-shape
-    // MinMax buckets; anything else runs the reference's op sequence.  The choice (and
-    // with it the pipelined exchange schedule) depends only on values equal on every
-    // rank; a rank whose tensors are not 16-B aligned runs on aligned copies
-    bool fused = allow_fused && method == BAGUA_COMPRESSION_MINMAX_UINT8 && t->num_elem == t->num_elem_allocated;
+    // fused kernels (csrc/kernels/decentralized.hip, mxfp4_ring.hip) for fully valid,
+    // same-shape MinMax and MXFP4 buckets; anything else runs the reference's op sequence.
+    // The choice (and with it the pipelined exchange schedule) depends only on values equal
+    // on every rank; a rank whose tensors are not 16-B aligned runs on aligned copies.
+    // BAGUA_MXFP4_RING_FUSED=0 (read per call, A/B): the op sequence for MXFP4.  It changes
+    // no byte on the wire and MXFP4 is never pipelined, so ranks need not agree on it.
+    const bool mx = method == BAGUA_COMPRESSION_MXFP4 && env_int("BAGUA_MXFP4_RING_FUSED", 1) != 0;
+    bool fused = allow_fused && (method == BAGUA_COMPRESSION_MINMAX_UINT8 || mx) &&
+                 t->num_elem == t->num_elem_allocated;
     for (const bagua_tensor_t* o : {weight, left, right})
         fused = fused && o->dtype == t->dtype && o->num_elem == t->num_elem;
     if (fused && (t->ptr % 16 || weight->ptr % 16 || left->ptr % 16 || right->ptr % 16))
@@ -1152,11 +1156,18 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
     const int sched = op_schedule(c, pieces, caller);
     const bool multipath =
         (caller & BAGUA_PIECES_MULTIPATH) ? (int)c->nranks >= kRingMinMultipath : ring_multipath_enabled(c);
-    const bool pipelined = fused && (pieces > 1 || multipath);
+    // (MXFP4 stays unpieced: one mix, one exchange, one apply, whatever the schedule asks for)
+    const bool pipelined = fused && !mx && (pieces > 1 || multipath);
     if ((rc = check_schedule(c, pipelined ? kOpRingPipelined : (allow_fused ? kOpRing : kOpRingUnfused), method, t,
                              (uint64_t)n, pipelined ? sched | (multipath ? BAGUA_PIECES_MULTIPATH : 0) : 1, 1)))
         return rc;
-    if (fused && !pipelined && c->nranks == 1 && env_int("BAGUA_ONE_RANK_FUSED", 1) != 0) {
+    if (mx && fused && c->nranks == 1 && env_int("BAGUA_ONE_RANK_FUSED", 1) != 0) {
+        // one rank: one pass over the four tensors, no payload (bagua_ring_one_rank_mxfp4)
+        rc = bagua_ring_one_rank_mxfp4(t->dtype, (void*)(uintptr_t)t->ptr, (void*)(uintptr_t)weight->ptr,
+                                       (void*)(uintptr_t)left->ptr, (void*)(uintptr_t)right->ptr, n, sp);
+        if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
+    }
+    if (fused && !mx && !pipelined && c->nranks == 1 && env_int("BAGUA_ONE_RANK_FUSED", 1) != 0) {
         // one rank: both peers' payloads are its own bytes, so the op is the mix pass and
         // one pass applying d = dq(q(mixed)) to all four tensors, no payload written
         // (bagua_ring_one_rank_minmax); BAGUA_ONE_RANK_FUSED=0: the steps below (A/B)
@@ -1180,7 +1191,13 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
     void* lp = (void*)(uintptr_t)left->ptr;
     void* rp = (void*)(uintptr_t)right->ptr;
     bool mixed = false;
-    if (fused) {
+    if (fused && mx) {
+        // :45-64 in one pass: the segment of the mixed t, which itself is never stored (every
+        // path below overwrites t before anything reads it)
+        rc = bagua_ring_mix_mxfp4(t->dtype, tp, lp, rp, wp, n, mine.as<uint8_t>(), S, sp);
+        if (rc == BAGUA_OK) mixed = true;
+        else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
+    } else if (fused) {
         // :45-64 t += L/3 + R/3 - 5W/3 (three rounded steps) with the min/max partials, then quantise
         const size_t wsb = bagua_minmax_u8_workspace_bytes(n, 1);
         uint64_t wsp = 0;
@@ -1262,8 +1279,9 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
     const bagua_tensor_t* from_r = p > 1 ? &rv : &mv;
     // :126-151
     if (fused) {
-        rc = bagua_ring_apply_minmax(t->dtype, mine.as<uint8_t>(), (const uint8_t*)(uintptr_t)from_l->ptr,
-                                     (const uint8_t*)(uintptr_t)from_r->ptr, S, n, tp, wp, lp, rp, sp);
+        rc = (mx ? bagua_ring_apply_mxfp4 : bagua_ring_apply_minmax)(
+            t->dtype, mine.as<uint8_t>(), (const uint8_t*)(uintptr_t)from_l->ptr,
+            (const uint8_t*)(uintptr_t)from_r->ptr, S, n, tp, wp, lp, rp, sp);
         if (rc == BAGUA_OK) return finish(c, BAGUA_OK);
         if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
     }

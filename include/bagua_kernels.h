@@ -263,6 +263,30 @@ int bagua_mxfp4_reduce_requantize_ef(int dtype, const uint8_t* input, size_t inp
                                      int num_chunks, int average, uint8_t* output, size_t output_bytes,
                                      int target_chunk, float* residual, bagua_stream_t stream);
 
+/* The decentralized ring op (decentralized_low_precision_synchronous.rs:45-64,126-151) with the
+ * MXFP4 codec, fused (MXFP4.md, "Ring op").  The segment is the num_chunks = 1 layout,
+ * bagua_mxfp4_compressed_bytes(num_elem, 1) bytes.  Byte for byte what the elementwise
+ * sequence leaves behind:
+ *   bagua_ring_mix_mxfp4: the segment of ((tensor + L/3) + R/3) + W*(-5/3), each step an
+ *     addmul as bagua_addmul_inplace computes it, as bagua_mxfp4_compress(num_chunks = 1)
+ *     would encode it.  `tensor` is not written.
+ *   bagua_ring_apply_mxfp4: L += dq(from_left); R += dq(from_right); tensor = dq(mine) + W;
+ *     W = tensor.  mine, from_left and from_right may be the same pointer.
+ *   bagua_ring_one_rank_mxfp4: the whole op at one rank (its own left and right peer) in one
+ *     pass, d = dq(q(mixed)) per element; no payload is written or read.
+ * One kernel each, no workspace.  BAGUA_ERR_UNSUPPORTED: a tensor that is not 16-B aligned
+ * (callers run the elementwise sequence) or a dtype other than F32 / F16 / BF16;
+ * BAGUA_ERR_INVALID_ARG: a null pointer, num_elem <= 0, a compressed buffer that is short
+ * or misaligned (16 B for the mix's output, 4 B for the apply's inputs).  Nothing is
+ * launched on a refusal. */
+int bagua_ring_mix_mxfp4(int dtype, const void* tensor, const void* left, const void* right, const void* weight,
+                         int num_elem, uint8_t* output, size_t output_bytes, bagua_stream_t stream);
+int bagua_ring_apply_mxfp4(int dtype, const uint8_t* mine, const uint8_t* from_left, const uint8_t* from_right,
+                           size_t compressed_bytes, int num_elem, void* tensor, void* weight, void* left, void* right,
+                           bagua_stream_t stream);
+int bagua_ring_one_rank_mxfp4(int dtype, void* tensor, void* weight, void* left, void* right, int num_elem,
+                              bagua_stream_t stream);
+
 /* ======================================================================== */
 /* v2 — chunk reduction and elementwise ops                                  */
 /* ======================================================================== */

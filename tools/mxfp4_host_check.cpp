@@ -5,14 +5,18 @@
 //   mxfp4_host_check decode MAXF_BITS < bytes > values.f32    (17 bytes in, 32 f32 out; NaN blocks as 0x7fc00000)
 //   mxfp4_host_check ef MAXF_BITS DTYPE < blocks.f32 > out   (32 x then 32 residuals in; 1 scale byte, 16 payload
 //                                                              bytes and the 32 new residuals out, per block)
+//   mxfp4_host_check ring MAXF_BITS DTYPE N < tensors > out  (t, w, l, r of N elements of T in; the four tensors
+//                                                              after one rank's ring op, then the segment, out)
 // MAXF_BITS: the f32 bits of the largest finite T, in hex; DTYPE: 0 f32, 1 f16, 2 bf16.
 // tests/test_mxfp4_cpu.py compares both directions with the numpy reference,
-// tests/test_mxfp4_ef_cpu.py the error-feedback rule.
+// tests/test_mxfp4_ef_cpu.py the error-feedback rule, tests/test_mxfp4_ring_cpu.py the ring op.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #include "mxfp4_common.hpp"
+#include "ring_mix.hpp"
 
 using namespace bagua;
 
@@ -33,7 +37,59 @@ static int run_ef(float maxf) {
     return 0;
 }
 
+// One rank's decentralized ring op (its own left and right peer): N elements of t, w, l, r in,
+// the four tensors after the op and the n_chunks = 1 segment of the mixed t out.
+template <int K>
+static int run_ring(int64_t n, float maxf) {
+    using T = MxT<K>;
+    using S = typename T::storage;
+    if (n <= 0) return 2;
+    std::vector<S> a[4];  // t, w, l, r
+    for (auto& v : a) {
+        v.resize((size_t)n);
+        if (fread(v.data(), sizeof(S), (size_t)n, stdin) != (size_t)n) return 3;
+    }
+    const float f13 = mx_ring_factor(K, 1.0 / 3.0), f53 = mx_ring_factor(K, -5.0 / 3.0);
+    const int64_t nb = mx_blocks(n), sbytes = mx_scale_bytes(n);
+    std::vector<uint8_t> seg((size_t)mx_segment_bytes(n), 0);
+    for (int64_t b = 0; b < nb; ++b) {
+        float m[kMxBlock];
+        for (int e = 0; e < kMxBlock; ++e) {  // elements at or past n count as +0 and are not read
+            const int64_t j = b * kMxBlock + e;
+            m[e] = j < n ? mix<T>(T::to_f(a[0][j]), T::to_f(a[2][j]), T::to_f(a[3][j]), T::to_f(a[1][j]), f13, f53) : 0.0f;
+        }
+        uint32_t byte, w[4];
+        mx_encode_block(m, maxf, byte, w);
+        seg[(size_t)b] = (uint8_t)byte;
+        memcpy(&seg[(size_t)(sbytes + b * kMxBlockBytes)], w, kMxBlockBytes);
+        for (int e = 0; e < kMxBlock; ++e) {
+            const int64_t j = b * kMxBlock + e;
+            if (j >= n) break;
+            const float d = mx_dq<T>((w[e / 8] >> (4 * (e % 8))) & 15u, byte, maxf);
+            float t = 0.0f, wt = T::to_f(a[1][j]), l = T::to_f(a[2][j]), r = T::to_f(a[3][j]);
+            mx_ring_apply<T>(d, d, d, t, wt, l, r);
+            a[0][j] = T::from_f(t);
+            a[1][j] = T::from_f(wt);
+            a[2][j] = T::from_f(l);
+            a[3][j] = T::from_f(r);
+        }
+    }
+    for (auto& v : a) fwrite(v.data(), sizeof(S), (size_t)n, stdout);
+    fwrite(seg.data(), 1, seg.size(), stdout);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc == 5 && !strcmp(argv[1], "ring")) {
+        const float m = mx_float((uint32_t)strtoul(argv[2], nullptr, 16));
+        const int64_t n = strtoll(argv[4], nullptr, 10);
+        switch (atoi(argv[3])) {
+            case 0: return run_ring<0>(n, m);
+            case 1: return run_ring<1>(n, m);
+            case 2: return run_ring<2>(n, m);
+        }
+        return 2;
+    }
     if (argc == 4 && !strcmp(argv[1], "ef")) {
         const float m = mx_float((uint32_t)strtoul(argv[2], nullptr, 16));
         switch (atoi(argv[3])) {
