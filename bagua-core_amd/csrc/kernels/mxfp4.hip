@@ -18,6 +18,7 @@
 // HW = true takes gfx950's conversions (v_cvt_scalef32_pk_fp4_f32 / _pk_f32_fp4) for the
 // rounding to and from E2M1; the scale byte, NaN blocks, the inf and largest-finite
 // clamps and the rounding to T stay in the arithmetic of mxfp4_common.hpp.
+#include <algorithm>
 #include <cstdint>
 
 #include "codec_common.hpp"
@@ -29,6 +30,9 @@ namespace bagua {
 
 constexpr int kMxItemBytes = 128;  // input bytes a lane of the encode has in flight per iteration
 constexpr int kMxDecodeVecs = 4;   // 16-B output vectors per lane per decode iteration
+// blocks between two piece boundaries: one wave tile of the 16-bit encode, two of the f32
+// encode; 128 scale bytes, 2 KiB of payload, 4096 elements
+constexpr int kMxGranule = 128;
 
 __device__ __forceinline__ int64_t mx_valid(int64_t in_num_elem, int64_t cs, int c) {
     const int64_t r = in_num_elem - (int64_t)c * cs;
@@ -68,11 +72,15 @@ __device__ __forceinline__ void mx_encode(const float (&x)[kMxBlock], float maxf
 // whole block instead (eight 16-B loads at a 128-B lane stride) took 116 us for 256 MiB of
 // f32 with nt loads against 49 us here, and 49 us with default-policy loads, which then
 // cost the decode behind it 15 us (profiles/r08_mxfp4_encode_variants.json).
+//
+// All three plain kernels work on blocks [bb, be) of their chunks (the whole chunk is
+// [0, nb)): bb is a multiple of kMxGranule, be another or nb, so a range starts on a wave
+// tile of every kernel and only the range that ends at nb has a ragged tile and the slack.
 // ------------------------------------------------------------------------
 template <typename T, bool HW>
 __global__ __launch_bounds__(kBlock) void mxfp4_encode_kernel(const typename T::storage* __restrict__ in,
                                                              int64_t in_num_elem, int64_t cs, int target,
-                                                             uint8_t* __restrict__ out) {
+                                                             uint8_t* __restrict__ out, int64_t bb, int64_t be) {
     using S = typename T::storage;
     constexpr int N = Vec<T>::N;        // elements per 16-B vector: 4 / 8
     constexpr int G = kMxBlock / N;     // lanes per block: 8 / 4
@@ -80,12 +88,15 @@ __global__ __launch_bounds__(kBlock) void mxfp4_encode_kernel(const typename T::
     constexpr int R = kMxItemBytes / 16;  // loads in flight per lane
     constexpr int TB = R * BW;          // blocks per wave tile (8 KiB of input)
     const int c = target < 0 ? (int)blockIdx.y : target;
-    const int64_t n = mx_valid(in_num_elem, cs, c);
-    const S* src = in + (int64_t)c * cs;
+    const int64_t sbytes = mx_scale_bytes(cs), pbytes = mx_payload_bytes(cs);
+    // everything below is relative to block bb of the chunk: the range's nb blocks, its n
+    // valid elements, their source, scale bytes and payload
+    const int64_t nb = be - bb, n = max(mx_valid(in_num_elem, cs, c) - bb * kMxBlock, (int64_t)0);
+    const S* src = in + (int64_t)c * cs + bb * kMxBlock;
     const bool vec = ((uintptr_t)src % 16) == 0;
-    const int64_t nb = mx_blocks(cs), sbytes = mx_scale_bytes(cs), pbytes = mx_payload_bytes(cs);
-    uint8_t* seg = out + (int64_t)c * (sbytes + pbytes);
-    uint8_t* pay = seg + sbytes;
+    uint8_t* seg = out + (int64_t)c * (sbytes + pbytes) + bb;
+    uint8_t* pay = seg + (sbytes - bb) + bb * kMxBlockBytes;
+    const bool last = be == mx_blocks(cs);  // this range ends the chunk: it writes the slack
     const int lane = lane_id(), sub = lane % G, lb = lane / G;
     const int64_t tiles = (nb + TB - 1) / TB;
     const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
@@ -143,9 +154,9 @@ __global__ __launch_bounds__(kBlock) void mxfp4_encode_kernel(const typename T::
             else reinterpret_cast<uint32_t*>(pay + b * kMxBlockBytes)[sub] = w;
             if (sub == 0) {
                 seg[b] = (uint8_t)byte;
-                if (b == nb - 1) {  // slack of both regions, zero
-                    for (int64_t q = nb; q < sbytes; ++q) seg[q] = 0;
-                    if (nb * kMxBlockBytes < pbytes)
+                if (last && b == nb - 1) {  // slack of both regions, zero
+                    for (int64_t q = nb; q < sbytes - bb; ++q) seg[q] = 0;
+                    if ((bb + nb) * kMxBlockBytes < pbytes)
                         *reinterpret_cast<uint4*>(pay + nb * kMxBlockBytes) = make_uint4(0u, 0u, 0u, 0u);
                 }
             }
@@ -158,17 +169,20 @@ __global__ __launch_bounds__(kBlock) void mxfp4_encode_kernel(const typename T::
 // ------------------------------------------------------------------------
 template <typename T, bool HW, bool NTS>
 __global__ __launch_bounds__(kBlock) void mxfp4_decode_kernel(const uint8_t* __restrict__ in, int64_t cs,
-                                                             typename T::storage* __restrict__ out) {
+                                                             typename T::storage* __restrict__ out, int64_t bb,
+                                                             int64_t be) {
     using S = typename T::storage;
     constexpr int N = Vec<T>::N;
     constexpr int KV = kMxDecodeVecs;
     const int c = blockIdx.y;
     const int64_t sbytes = mx_scale_bytes(cs);
-    const uint8_t* seg = in + (int64_t)c * (sbytes + mx_payload_bytes(cs));
-    const uint8_t* pay = seg + sbytes;
-    S* dst = out + (int64_t)c * cs;
+    // relative to block bb of the chunk: scale bytes, payload, output and the range's n elements
+    const uint8_t* seg = in + (int64_t)c * (sbytes + mx_payload_bytes(cs)) + bb;
+    const uint8_t* pay = seg + (sbytes - bb) + bb * kMxBlockBytes;
+    S* dst = out + (int64_t)c * cs + bb * kMxBlock;
     const bool vec = ((uintptr_t)dst % 16) == 0;
-    const int64_t nvec = (cs + N - 1) / N;
+    const int64_t n = min(cs, be * kMxBlock) - bb * kMxBlock;
+    const int64_t nvec = (n + N - 1) / N;
     for (int64_t v0 = (int64_t)blockIdx.x * (kBlock * KV) + threadIdx.x; v0 < nvec;
          v0 += (int64_t)gridDim.x * (kBlock * KV)) {
         uint32_t w[KV], sb[KV];
@@ -189,14 +203,14 @@ __global__ __launch_bounds__(kBlock) void mxfp4_decode_kernel(const uint8_t* __r
             if (v0 + k * kBlock >= nvec) break;
             uint32_t u[N];
             mx_decode<T, HW, N / 2>(w[k], sb[k], u);
-            if (vec && j + N <= cs) {
+            if (vec && j + N <= n) {
                 const uint4 q = pack_stored<T>(u);
                 if constexpr (NTS) nt_store16(q, dst + j);
                 else *reinterpret_cast<uint4*>(dst + j) = q;
             } else {
 #pragma unroll
                 for (int e = 0; e < N; ++e)
-                    if (j + e < cs) dst[j + e] = storage_from_bits<T>(u[e]);
+                    if (j + e < n) dst[j + e] = storage_from_bits<T>(u[e]);
             }
         }
     }
@@ -212,14 +226,15 @@ template <typename T, int BY, bool HW, bool STORE>
 __global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_kernel(const uint8_t* __restrict__ in, int64_t cs, int p,
                                                                     int average,
                                                                     typename T::storage* __restrict__ chunk,
-                                                                    uint8_t* __restrict__ out_seg) {
+                                                                    uint8_t* __restrict__ out_seg, int64_t bb,
+                                                                    int64_t be) {
     constexpr int N = Vec<T>::N;
     const int64_t nb = mx_blocks(cs), sbytes = mx_scale_bytes(cs), pbytes = mx_payload_bytes(cs);
     const int64_t segb = sbytes + pbytes;
     uint8_t* pay_out = out_seg + sbytes;
     const bool vec = STORE && ((uintptr_t)chunk % 16) == 0;
     const float pf = (float)p, maxf = T::init_max();
-    for (int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; b < nb; b += (int64_t)gridDim.x * kBlock) {
+    for (int64_t b = bb + (int64_t)blockIdx.x * kBlock + threadIdx.x; b < be; b += (int64_t)gridDim.x * kBlock) {
         float x[kMxBlock];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {  // eight elements (one payload word) of every segment at a time
@@ -544,90 +559,111 @@ __global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_ef_kernel(const ui
 // ------------------------------------------------------------------------
 // mx_hw() and mx_grid(): mxfp4_device.hpp
 
+// A block range [bb, be) of a chunk of cs elements as the range entries take it: bb a
+// multiple of the granule in [0, nb], be in [bb, nb] and either nb or a multiple of it.
+// The whole-chunk entries pass kMxWhole for [0, nb).
+constexpr int kMxWhole = -1;
+static bool mx_range(int cs, int& bb, int& be) {
+    const int nb = (int)mx_blocks(cs);
+    if (bb == kMxWhole && be == kMxWhole) {
+        bb = 0;
+        be = nb;
+        return true;
+    }
+    return bb >= 0 && bb <= nb && bb % kMxGranule == 0 && be >= bb && be <= nb && (be == nb || be % kMxGranule == 0);
+}
+
 template <typename T>
 static int mx_compress_impl(const void* input, int in_num_elem, int cs, int p, uint8_t* out, size_t out_bytes,
-                            int target, hipStream_t s) {
+                            int target, int bb, int be, hipStream_t s) {
     using S = typename T::storage;
     if (p <= 0 || p > 65535 || cs < 0 || in_num_elem < 0 || target < -1 || target >= p || !out || !input)
         return BAGUA_ERR_INVALID_ARG;
     if (out_bytes < (size_t)p * (size_t)mx_segment_bytes(cs)) return BAGUA_ERR_INVALID_ARG;
     if ((uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;  // payload words and the 16-B slack store are aligned stores
-    if (cs == 0) return BAGUA_OK;
-    // a wave tile is 8 KiB of input, a workgroup four of them
-    constexpr int64_t kTileElems = kMxItemBytes * kWave / (int64_t)sizeof(S);
+    if (!mx_range(cs, bb, be)) return BAGUA_ERR_INVALID_ARG;
+    if (bb == be) return BAGUA_OK;
+    // a wave tile is 8 KiB of input, a workgroup four of them; the grid covers the range
+    constexpr int64_t kTileBlocks = kMxItemBytes * kWave / (int64_t)sizeof(S) / kMxBlock;
     const int nact = target < 0 ? p : 1;
-    const dim3 grid(mx_grid(((int64_t)cs + kTileElems - 1) / kTileElems, kWavesPerBlock, nact, "BAGUA_TUNE_MX_ENCODE_BLOCKS"),
+    const dim3 grid(mx_grid(((int64_t)(be - bb) + kTileBlocks - 1) / kTileBlocks, kWavesPerBlock, nact,
+                            "BAGUA_TUNE_MX_ENCODE_BLOCKS"),
                     nact);
     if (mx_hw())
         launch(mxfp4_encode_kernel<T, true>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
-               (int64_t)in_num_elem, (int64_t)cs, target, out);
+               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be);
     else
         launch(mxfp4_encode_kernel<T, false>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
-               (int64_t)in_num_elem, (int64_t)cs, target, out);
+               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be);
     return check_launch();
 }
 
 template <typename T, bool HW>
 static void mx_launch_decode(const dim3& grid, bool nt, const uint8_t* in, int64_t cs, typename T::storage* out,
-                             hipStream_t s) {
-    if (nt) launch(mxfp4_decode_kernel<T, HW, true>, grid, dim3(kBlock), 0, s, in, cs, out);
-    else launch(mxfp4_decode_kernel<T, HW, false>, grid, dim3(kBlock), 0, s, in, cs, out);
+                             int64_t bb, int64_t be, hipStream_t s) {
+    if (nt) launch(mxfp4_decode_kernel<T, HW, true>, grid, dim3(kBlock), 0, s, in, cs, out, bb, be);
+    else launch(mxfp4_decode_kernel<T, HW, false>, grid, dim3(kBlock), 0, s, in, cs, out, bb, be);
 }
 
 template <typename T>
-static int mx_decompress_impl(const uint8_t* in, size_t in_bytes, int cs, int p, void* out, hipStream_t s) {
+static int mx_decompress_impl(const uint8_t* in, size_t in_bytes, int cs, int p, void* out, int bb, int be,
+                              hipStream_t s) {
     using S = typename T::storage;
     if (p <= 0 || p > 65535 || cs < 0 || !in || !out) return BAGUA_ERR_INVALID_ARG;
     if (in_bytes < (size_t)p * (size_t)mx_segment_bytes(cs)) return BAGUA_ERR_INVALID_ARG;
     if ((uintptr_t)in % 4) return BAGUA_ERR_INVALID_ARG;  // payload read as 2- and 4-B words
-    if (cs == 0) return BAGUA_OK;
-    // store policy by the bucket's size, as the 1-bit decode's (onebit.hip): past the
+    if (!mx_range(cs, bb, be)) return BAGUA_ERR_INVALID_ARG;
+    if (bb == be) return BAGUA_OK;
+    // store policy by the bucket's size (not the range's), as the 1-bit decode's (onebit.hip): past the
     // 256 MiB Infinity Cache the dirty lines cannot stay on chip; BAGUA_MX_DECODE_NT=0 / 1 forces either
     const int env = tune_int("BAGUA_MX_DECODE_NT", -1);
     const bool nt = env >= 0 ? env != 0 : (int64_t)cs * p * (int64_t)sizeof(S) > ((int64_t)256 << 20);
-    const int64_t nvec = (cs + Vec<T>::N - 1) / Vec<T>::N;
+    constexpr int N = Vec<T>::N;
+    const int64_t last = std::min(((int64_t)cs + N - 1) / N, (int64_t)be * (kMxBlock / N));
+    const int64_t nvec = last - (int64_t)bb * (kMxBlock / N);  // the range's 16-B output vectors
     const dim3 grid(mx_grid(nvec, kBlock * kMxDecodeVecs, p, "BAGUA_TUNE_MX_DECODE_BLOCKS"), p);
-    if (mx_hw()) mx_launch_decode<T, true>(grid, nt, in, (int64_t)cs, static_cast<S*>(out), s);
-    else mx_launch_decode<T, false>(grid, nt, in, (int64_t)cs, static_cast<S*>(out), s);
+    if (mx_hw()) mx_launch_decode<T, true>(grid, nt, in, (int64_t)cs, static_cast<S*>(out), bb, be, s);
+    else mx_launch_decode<T, false>(grid, nt, in, (int64_t)cs, static_cast<S*>(out), bb, be, s);
     return check_launch();
 }
 
 template <typename T, int BY, bool HW>
 static void mx_launch_reduce(int blocks, const uint8_t* in, int64_t cs, int p, int average,
-                             typename T::storage* chunk, uint8_t* seg, hipStream_t s) {
+                             typename T::storage* chunk, uint8_t* seg, int64_t bb, int64_t be, hipStream_t s) {
     if (chunk)
         launch(mxfp4_reduce_encode_kernel<T, BY, HW, true>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average,
-               chunk, seg);
+               chunk, seg, bb, be);
     else
         launch(mxfp4_reduce_encode_kernel<T, BY, HW, false>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average,
-               chunk, seg);
+               chunk, seg, bb, be);
 }
 
 template <typename T, bool HW>
 static void mx_dispatch_reduce(int blocks, const uint8_t* in, int64_t cs, int p, int average,
-                               typename T::storage* chunk, uint8_t* seg, hipStream_t s) {
+                               typename T::storage* chunk, uint8_t* seg, int64_t bb, int64_t be, hipStream_t s) {
     switch (reduce_by(p)) {
-        case 2: mx_launch_reduce<T, 2, HW>(blocks, in, cs, p, average, chunk, seg, s); break;
-        case 4: mx_launch_reduce<T, 4, HW>(blocks, in, cs, p, average, chunk, seg, s); break;
-        default: mx_launch_reduce<T, 8, HW>(blocks, in, cs, p, average, chunk, seg, s); break;
+        case 2: mx_launch_reduce<T, 2, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, s); break;
+        case 4: mx_launch_reduce<T, 4, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, s); break;
+        default: mx_launch_reduce<T, 8, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, s); break;
     }
 }
 
 template <typename T>
 static int mx_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, int cs, int p, void* tensor, int average,
-                                     uint8_t* out, size_t out_bytes, int target, hipStream_t s) {
+                                     uint8_t* out, size_t out_bytes, int target, int bb, int be, hipStream_t s) {
     using S = typename T::storage;
     if (p <= 0 || cs < 0 || target < 0 || target >= p || !recv || !out) return BAGUA_ERR_INVALID_ARG;
     if (p > kMaxFusedChunks) return BAGUA_ERR_UNSUPPORTED;  // caller runs decompress + reduce + compress
     const size_t segb = (size_t)mx_segment_bytes(cs);
     if (recv_bytes < (size_t)p * segb || out_bytes < (size_t)p * segb) return BAGUA_ERR_INVALID_ARG;
     if ((uintptr_t)recv % 4 || (uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;
-    if (cs == 0) return BAGUA_OK;
+    if (!mx_range(cs, bb, be)) return BAGUA_ERR_INVALID_ARG;
+    if (bb == be) return BAGUA_OK;
     S* chunk = tensor ? static_cast<S*>(tensor) + (int64_t)target * cs : nullptr;  // nullptr: not stored
     uint8_t* seg = out + (size_t)target * segb;
-    const int blocks = mx_grid(mx_blocks(cs), kBlock, 1, "BAGUA_TUNE_MX_MIDDLE_BLOCKS");
-    if (mx_hw()) mx_dispatch_reduce<T, true>(blocks, recv, (int64_t)cs, p, average, chunk, seg, s);
-    else mx_dispatch_reduce<T, false>(blocks, recv, (int64_t)cs, p, average, chunk, seg, s);
+    const int blocks = mx_grid(be - bb, kBlock, 1, "BAGUA_TUNE_MX_MIDDLE_BLOCKS");
+    if (mx_hw()) mx_dispatch_reduce<T, true>(blocks, recv, (int64_t)cs, p, average, chunk, seg, bb, be, s);
+    else mx_dispatch_reduce<T, false>(blocks, recv, (int64_t)cs, p, average, chunk, seg, bb, be, s);
     return check_launch();
 }
 
@@ -753,50 +789,127 @@ size_t bagua_mxfp4_compressed_bytes(int chunk_size, int num_chunks) {
     return (size_t)num_chunks * (size_t)mx_segment_bytes(chunk_size);
 }
 
-int bagua_mxfp4_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
-                         uint8_t* output, size_t output_bytes, int target_chunk, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// the whole-chunk entries are the range [0, nb) (kMxWhole) of the range entries' code
+static int mx_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                       uint8_t* output, size_t output_bytes, int target_chunk, int bb, int be, hipStream_t s) {
     switch (dtype) {
         case BAGUA_DTYPE_F32:
             return mx_compress_impl<F32>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                         target_chunk, s);
+                                         target_chunk, bb, be, s);
         case BAGUA_DTYPE_F16:
             return mx_compress_impl<F16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                         target_chunk, s);
+                                         target_chunk, bb, be, s);
         case BAGUA_DTYPE_BF16:
             return mx_compress_impl<BF16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                          target_chunk, s);
+                                          target_chunk, bb, be, s);
     }
     return BAGUA_ERR_UNSUPPORTED;
 }
 
-int bagua_mxfp4_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
-                           void* output, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
+static int mx_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                         void* output, int bb, int be, hipStream_t s) {
     switch (dtype) {
-        case BAGUA_DTYPE_F32: return mx_decompress_impl<F32>(input, input_bytes, chunk_size, num_chunks, output, s);
-        case BAGUA_DTYPE_F16: return mx_decompress_impl<F16>(input, input_bytes, chunk_size, num_chunks, output, s);
-        case BAGUA_DTYPE_BF16: return mx_decompress_impl<BF16>(input, input_bytes, chunk_size, num_chunks, output, s);
+        case BAGUA_DTYPE_F32:
+            return mx_decompress_impl<F32>(input, input_bytes, chunk_size, num_chunks, output, bb, be, s);
+        case BAGUA_DTYPE_F16:
+            return mx_decompress_impl<F16>(input, input_bytes, chunk_size, num_chunks, output, bb, be, s);
+        case BAGUA_DTYPE_BF16:
+            return mx_decompress_impl<BF16>(input, input_bytes, chunk_size, num_chunks, output, bb, be, s);
     }
     return BAGUA_ERR_UNSUPPORTED;
+}
+
+static int mx_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                                void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
+                                int bb, int be, hipStream_t s) {
+    switch (dtype) {
+        case BAGUA_DTYPE_F32:
+            return mx_reduce_requantize_impl<F32>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
+                                                  output_bytes, target_chunk, bb, be, s);
+        case BAGUA_DTYPE_F16:
+            return mx_reduce_requantize_impl<F16>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
+                                                  output_bytes, target_chunk, bb, be, s);
+        case BAGUA_DTYPE_BF16:
+            return mx_reduce_requantize_impl<BF16>(input, input_bytes, chunk_size, num_chunks, tensor, average,
+                                                   output, output_bytes, target_chunk, bb, be, s);
+    }
+    return BAGUA_ERR_UNSUPPORTED;
+}
+
+int bagua_mxfp4_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                         uint8_t* output, size_t output_bytes, int target_chunk, bagua_stream_t stream) {
+    return mx_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, target_chunk,
+                       kMxWhole, kMxWhole, static_cast<hipStream_t>(stream));
+}
+
+int bagua_mxfp4_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                           void* output, bagua_stream_t stream) {
+    return mx_decompress(dtype, input, input_bytes, chunk_size, num_chunks, output, kMxWhole, kMxWhole,
+                         static_cast<hipStream_t>(stream));
 }
 
 int bagua_mxfp4_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
                                   void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
                                   bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return mx_reduce_requantize_impl<F32>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
-                                                  output_bytes, target_chunk, s);
-        case BAGUA_DTYPE_F16:
-            return mx_reduce_requantize_impl<F16>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
-                                                  output_bytes, target_chunk, s);
-        case BAGUA_DTYPE_BF16:
-            return mx_reduce_requantize_impl<BF16>(input, input_bytes, chunk_size, num_chunks, tensor, average,
-                                                   output, output_bytes, target_chunk, s);
+    return mx_reduce_requantize(dtype, input, input_bytes, chunk_size, num_chunks, tensor, average, output,
+                                output_bytes, target_chunk, kMxWhole, kMxWhole, static_cast<hipStream_t>(stream));
+}
+
+// ---- pieces (MXFP4.md, "Pipelined op") ----
+// Piece `piece` of schedule `pieces` as a block range: bagua_minmax_u8_piece_range's rule
+// on nb blocks with edges rounded up to the granule.  Tapered from 3 pieces on: edge
+// weights 0, 1, 3, ..., 2(k - 1), so the first and the last piece are half size.
+int bagua_mxfp4_piece_range(int chunk_size, int pieces, int piece, int* block_begin, int* block_end) {
+    const int count = pieces & BAGUA_PIECES_COUNT_MASK;
+    if (chunk_size < 0 || count < 1 || piece < 0 || piece >= count || !block_begin || !block_end ||
+        (pieces & ~(BAGUA_PIECES_COUNT_MASK | BAGUA_PIECES_TAPERED | BAGUA_PIECES_MULTIPATH | BAGUA_PIECES_FOLDED |
+                    BAGUA_PIECES_TABLES)))
+        return BAGUA_ERR_INVALID_ARG;
+    const int64_t nb = mx_blocks(chunk_size);
+    auto clip = [&](int64_t blocks) -> int {
+        const int64_t x = (blocks + kMxGranule - 1) / kMxGranule * kMxGranule;
+        return (int)(x < nb ? x : nb);
+    };
+    if (count >= 3 && (pieces & BAGUA_PIECES_TAPERED)) {
+        const int64_t W = 2 * (int64_t)(count - 1);
+        // edge j at weight 2j - 1 of W, rounded up, and at least a granule past edge j - 1: a
+        // chunk of fewer than W granules then fills its first pieces and leaves its last ones
+        // empty (with W granules or more the rounded edges are a granule apart by themselves)
+        int64_t e = 0;
+        for (int j = 1; j <= piece + 1; ++j) {
+            if (j == piece + 1) *block_begin = (int)e;
+            e = j >= count ? nb : clip(std::max((nb * (2 * (int64_t)j - 1) + W - 1) / W, e + kMxGranule));
+        }
+        *block_end = (int)e;
+    } else {
+        const int64_t L = clip((nb + count - 1) / count);  // nb < L only when one piece holds everything
+        *block_begin = (int)std::min((int64_t)piece * L, nb);
+        *block_end = (int)std::min(((int64_t)piece + 1) * L, nb);
     }
-    return BAGUA_ERR_UNSUPPORTED;
+    return BAGUA_OK;
+}
+
+int bagua_mxfp4_compress_range(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                               uint8_t* output, size_t output_bytes, int block_begin, int block_end,
+                               bagua_stream_t stream) {
+    if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
+    return mx_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, -1,
+                       block_begin, block_end, static_cast<hipStream_t>(stream));
+}
+
+int bagua_mxfp4_decompress_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                                 void* output, int block_begin, int block_end, bagua_stream_t stream) {
+    if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
+    return mx_decompress(dtype, input, input_bytes, chunk_size, num_chunks, output, block_begin, block_end,
+                         static_cast<hipStream_t>(stream));
+}
+
+int bagua_mxfp4_reduce_requantize_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                        int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                        int target_chunk, int block_begin, int block_end, bagua_stream_t stream) {
+    if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
+    return mx_reduce_requantize(dtype, input, input_bytes, chunk_size, num_chunks, nullptr, average, output,
+                                output_bytes, target_chunk, block_begin, block_end, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

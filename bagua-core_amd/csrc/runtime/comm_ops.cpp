@@ -152,7 +152,7 @@ int env_int(const char* name, long dflt);
 int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_tensor_t* t, uint64_t chunk,
                    int sched, int average);
 enum { kOpCentralized = 1, kOpCentralizedUnfused, kOpCentralizedPipelined, kOpOneBitPipelined, kOpRing,
-       kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback };
+       kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback, kOpMxfp4Pipelined };
 
 int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int method, bool fused) {
     OpTimer tm;
@@ -470,29 +470,47 @@ void onebit_piece_bytes(const Chunking& k, int tb, int te, bool header, size_t* 
     if (!header && tb >= te) *lo = *hi = 0;
 }
 
-// one piece of the alltoall (send -> recv) or of the in-place allgather (send)
-int exchange_piece(BaguaSingleCommunicatorC* c, const Chunking& k, uint8_t* send, uint8_t* recv, size_t lo,
-                   size_t hi, bool alltoall) {
-    if (hi <= lo) return BAGUA_OK;
-    const size_t co = k.S / k.p, len = hi - lo;
+// one piece of the alltoall (send -> recv) or of the in-place allgather (send): the byte
+// ranges r[0 .. nr) of every segment in one group, each pair's transfers posted in range
+// order on both ends; empty ranges move nothing
+struct ByteRange {
+    size_t lo, hi;
+};
+int exchange_ranges(BaguaSingleCommunicatorC* c, const Chunking& k, uint8_t* send, uint8_t* recv, const ByteRange* r,
+                    int nr, bool alltoall) {
+    bool any = false;
+    for (int i = 0; i < nr; ++i) any = any || r[i].hi > r[i].lo;
+    if (!any) return BAGUA_OK;
+    const size_t co = k.S / k.p;
     hipStream_t s1 = c->side;
-    if (alltoall &&
-        hipMemcpyAsync(recv + k.rank * co + lo, send + k.rank * co + lo, len, hipMemcpyDeviceToDevice, s1) != hipSuccess)
-        return BAGUA_ERR_HIP;
+    for (int i = 0; i < nr && alltoall; ++i)
+        if (r[i].hi > r[i].lo && hipMemcpyAsync(recv + k.rank * co + r[i].lo, send + k.rank * co + r[i].lo,
+                                                r[i].hi - r[i].lo, hipMemcpyDeviceToDevice, s1) != hipSuccess)
+            return BAGUA_ERR_HIP;
     if (k.p == 1) return BAGUA_OK;
     int rc = c->t->group_start();
     for (int j = 0; j < k.p && !rc; ++j) {
         if (j == k.rank) continue;
-        if (alltoall) {
-            rc = c->t->send(send + j * co + lo, len, BAGUA_DTYPE_U8, j, s1);
-            if (!rc) rc = c->t->recv(recv + j * co + lo, len, BAGUA_DTYPE_U8, j, s1);
-        } else {
-            rc = c->t->send(send + k.rank * co + lo, len, BAGUA_DTYPE_U8, j, s1);
-            if (!rc) rc = c->t->recv(send + j * co + lo, len, BAGUA_DTYPE_U8, j, s1);
+        for (int i = 0; i < nr && !rc; ++i) {
+            if (r[i].hi <= r[i].lo) continue;
+            const size_t lo = r[i].lo, len = r[i].hi - lo;
+            if (alltoall) {
+                rc = c->t->send(send + j * co + lo, len, BAGUA_DTYPE_U8, j, s1);
+                if (!rc) rc = c->t->recv(recv + j * co + lo, len, BAGUA_DTYPE_U8, j, s1);
+            } else {
+                rc = c->t->send(send + k.rank * co + lo, len, BAGUA_DTYPE_U8, j, s1);
+                if (!rc) rc = c->t->recv(send + j * co + lo, len, BAGUA_DTYPE_U8, j, s1);
+            }
         }
     }
     const int rc_end = c->t->group_end();
     return rc ? rc : rc_end;
+}
+
+int exchange_piece(BaguaSingleCommunicatorC* c, const Chunking& k, uint8_t* send, uint8_t* recv, size_t lo,
+                   size_t hi, bool alltoall) {
+    const ByteRange r{lo, hi};
+    return exchange_ranges(c, k, send, recv, &r, 1, alltoall);
 }
 
 int finish_both(BaguaSingleCommunicatorC* c, int rc) {
@@ -827,6 +845,103 @@ int centralized_onebit_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
     return finish_both(c, BAGUA_OK);
 }
 
+// The MXFP4 op, pipelined (MXFP4.md, "Pipelined op").  Every 32-element block carries its
+// own scale byte, so nothing of a chunk is needed before its first bytes leave and the
+// middle step of a piece needs no other piece: piece q is encoded and sent, reduced and
+// re-encoded as soon as it has arrived, gathered and decoded, independently of the others.
+// No workspace.  A piece is a block range of every chunk (bagua_mxfp4_piece_range), in a
+// segment the scale bytes [bb, be) and the payload bytes [sbytes + 16 bb, sbytes + 16 be);
+// the last non-empty piece's ranges run to the end of their regions (the slack).
+//
+//   stream: E0 E1 .. Ek | M0 M1 .. Mk | D0 D1 .. Dk
+//   side  :    A0 A1 .. Ak     G0 G1 .. Gk
+//   (E encode piece q of all chunks, A its alltoall, M the fused middle step on piece q of
+//    the own chunk, G its allgather, D decode piece q of all chunks; M_q waits for A_q
+//    only, G_q for M_q, D_q for G_q; the side stream posts A0 .. Ak, then G0 .. Gk)
+void mxfp4_piece_bytes(const Chunking& k, int bb, int be, ByteRange (&r)[2]) {
+    const size_t nb = (k.cs + 31) / 32, sbytes = (nb + 31) / 32 * 32, co = k.S / k.p;
+    r[0] = r[1] = ByteRange{0, 0};
+    if (bb >= be) return;
+    const bool last = (size_t)be == nb;
+    r[0] = ByteRange{(size_t)bb, last ? sbytes : (size_t)be};
+    r[1] = ByteRange{sbytes + 16 * (size_t)bb, last ? co : sbytes + 16 * (size_t)be};
+}
+
+int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int pieces) {
+    Chunking k;
+    if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
+    int rc = plan(c, t, BAGUA_COMPRESSION_MXFP4, &k);
+    if (rc) return rc;
+    const int caller = pieces;
+    pieces &= BAGUA_PIECES_COUNT_MASK;
+    if (pieces < 1) pieces = k.p == 1 ? 1 : auto_pieces(c, k.S / k.p);  // segment bytes per chunk
+    // unpieced: one rank (no exchange to hide) and the shapes the fused middle step or the
+    // vector paths cannot take -- decided from values equal on every rank only
+    if (pieces == 1 || k.p == 1 || k.p > 16 || t->num_elem != t->num_elem_allocated || k.cs > 0x7fffffffULL ||
+        (k.cs * bagua_dtype_bytes(t->dtype)) % 16)
+        return centralized(c, t, average, BAGUA_COMPRESSION_MXFP4, true);
+    if (t->ptr % 16)  // this rank alone: the same schedule on an aligned staging copy
+        return with_aligned_copy(c, {t}, [&](const std::vector<const bagua_tensor_t*>& u) {
+            return centralized_pipelined_mxfp4(c, u[0], average, caller);
+        });
+    const int sched = op_schedule(c, pieces, caller);
+    DeviceGuard guard(c->device_id);
+    if ((rc = check_schedule(c, kOpMxfp4Pipelined, BAGUA_COMPRESSION_MXFP4, t, k.cs, sched, average))) return rc;
+    if (c->ensure_side(4 * (size_t)pieces + 1)) return BAGUA_ERR_HIP;
+    hipStream_t s0 = c->stream, s1 = c->side;
+    hipEvent_t* encoded = c->events.data();
+    hipEvent_t* exchanged = encoded + pieces;
+    hipEvent_t* requantised = exchanged + pieces;
+    hipEvent_t* gathered = requantised + pieces;
+    hipEvent_t start = gathered[pieces];
+    const int dt = t->dtype, cs = (int)k.cs, p = k.p;
+    void* x = (void*)(uintptr_t)t->ptr;
+    OpBuffer send(c), recv(c);
+    TRY(send.allocate(c->device_id, k.S));
+    TRY(recv.allocate(c->device_id, k.S));
+    uint8_t* sb = send.as<uint8_t>();
+    uint8_t* rb = recv.as<uint8_t>();
+    std::vector<int> bb(pieces), be(pieces);
+    for (int q = 0; q < pieces; ++q) TRY(bagua_mxfp4_piece_range(cs, sched, q, &bb[q], &be[q]));
+    ByteRange r[2];
+    // the side stream starts after everything already queued on the op's stream
+    HIP2(hipEventRecord(start, s0));
+    HIP2(hipStreamWaitEvent(s1, start, 0));
+    // 1. encode + alltoall piece by piece (an empty piece launches and moves nothing, its
+    // events are recorded all the same)
+    for (int q = 0; q < pieces; ++q) {
+        if (bb[q] < be[q])
+            TRY2(bagua_mxfp4_compress_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, bb[q], be[q], s0));
+        HIP2(hipEventRecord(encoded[q], s0));
+    }
+    for (int q = 0; q < pieces; ++q) {
+        mxfp4_piece_bytes(k, bb[q], be[q], r);
+        HIP2(hipStreamWaitEvent(s1, encoded[q], 0));
+        TRY2(exchange_ranges(c, k, sb, rb, r, 2, true));
+        HIP2(hipEventRecord(exchanged[q], s1));
+    }
+    // 2. the middle step of piece q as soon as it has arrived: decode the p received versions,
+    // reduce, re-encode into the own segment (the reduced chunk is not stored)
+    for (int q = 0; q < pieces; ++q) {
+        HIP2(hipStreamWaitEvent(s0, exchanged[q], 0));
+        if (bb[q] < be[q])
+            TRY2(bagua_mxfp4_reduce_requantize_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, bb[q], be[q], s0));
+        HIP2(hipEventRecord(requantised[q], s0));
+    }
+    // 3. allgather + decode piece by piece
+    for (int q = 0; q < pieces; ++q) {
+        mxfp4_piece_bytes(k, bb[q], be[q], r);
+        HIP2(hipStreamWaitEvent(s1, requantised[q], 0));
+        TRY2(exchange_ranges(c, k, sb, rb, r, 2, false));
+        HIP2(hipEventRecord(gathered[q], s1));
+    }
+    for (int q = 0; q < pieces; ++q) {
+        HIP2(hipStreamWaitEvent(s0, gathered[q], 0));
+        if (bb[q] < be[q]) TRY2(bagua_mxfp4_decompress_range(dt, sb, k.S, cs, p, x, bb[q], be[q], s0));
+    }
+    return finish_both(c, BAGUA_OK);
+}
+
 // The MXFP4 op with error feedback (MXFP4.md): centralized()'s steps for the MXFP4 codec
 // with the two `_ef` kernels.  The worker residual compensates what this rank encodes for
 // the alltoall, the server residual the own chunk it re-encodes for the allgather; wire
@@ -1058,6 +1173,7 @@ extern "C" {
 int bagua_centralized_low_precision_pipelined(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
                                               int method, int pieces) {
     if (method == BAGUA_COMPRESSION_ONEBIT) return centralized_pipelined_onebit(c, t, average, pieces);
+    if (method == BAGUA_COMPRESSION_MXFP4) return centralized_pipelined_mxfp4(c, t, average, pieces);
     if (method != BAGUA_COMPRESSION_MINMAX_UINT8) return centralized(c, t, average, method, true);
     return centralized_pipelined(c, t, average, pieces);
 }

@@ -182,8 +182,9 @@ int bagua_centralized_low_precision_synchronous(BaguaSingleCommunicatorC* comm, 
  * the next; bit-identical to the unpieced op.  pieces = 0 picks automatically
  * (BAGUA_PIPELINE_PIECES cap, default 4; BAGUA_PIPELINE_MIN_PIECE payload bytes
  * per chunk piece, default 1 MiB; one rank: unpieced), 1 disables; the op above
- * runs this with pieces = 0.  MinMaxUInt8 and the 1-bit codec; shapes the fused
- * kernels cannot take run unpieced. */
+ * runs this with pieces = 0.  MinMaxUInt8, the 1-bit codec and MXFP4 (pieces of
+ * whole 32-element blocks, the payload counted in segment bytes; MXFP4.md,
+ * "Pipelined op"); shapes the fused kernels cannot take run unpieced. */
 int bagua_centralized_low_precision_pipelined(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t, int average,
                                               int method, int pieces);
 /* The 1-bit op with error feedback: the pipelined op above with the

@@ -238,6 +238,36 @@ int bagua_mxfp4_reduce_requantize(int dtype, const uint8_t* input, size_t input_
                                   void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
                                   bagua_stream_t stream);
 
+/* Pieced MXFP4 codec (the pipelined centralized op; MXFP4.md, "Pipelined op").  Every block
+ * is self-contained, so a piece is a block range [block_begin, block_end) of every chunk:
+ * scale bytes [bb, be) and payload bytes [sbytes + 16 bb, sbytes + 16 be) of each segment.
+ * Boundaries are multiples of a granule of 128 blocks (4096 elements) except the chunk's end
+ * nb = ceil(chunk_size / 32).
+ *   bagua_mxfp4_piece_range: piece `piece` of schedule `pieces` (a count, optionally OR-ed
+ *     with BAGUA_PIECES_TAPERED, as for bagua_minmax_u8_piece_range below); edges rounded
+ *     up to the granule and clipped to nb.  The ranges partition [0, nb); trailing ones may
+ *     be empty.  Host-only.
+ *   The three range entries are the whole-chunk entries above restricted to the range: the
+ *     same kernels, argument rules and refusals, and the whole-chunk entries are the range
+ *     [0, nb).  bagua_mxfp4_compress_range encodes the range of every chunk,
+ *     bagua_mxfp4_decompress_range writes elements [32 bb, min(32 be, chunk_size)) of every
+ *     chunk, bagua_mxfp4_reduce_requantize_range is the middle step on the range of chunk
+ *     `target_chunk` (the reduced chunk is not stored).  The range that ends at nb writes
+ *     the zero slack of both regions; no other byte outside the two ranges is touched.
+ *     BAGUA_ERR_INVALID_ARG: block_begin not a multiple of 128 or outside [0, nb];
+ *     block_end below block_begin, above nb, or neither nb nor a multiple of 128.  An empty
+ *     range launches nothing and returns BAGUA_OK; callers skip the empty pieces of a
+ *     schedule (their block_begin is nb, which need not be a multiple of 128). */
+int bagua_mxfp4_piece_range(int chunk_size, int pieces, int piece, int* block_begin, int* block_end);
+int bagua_mxfp4_compress_range(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                               uint8_t* output, size_t output_bytes, int block_begin, int block_end,
+                               bagua_stream_t stream);
+int bagua_mxfp4_decompress_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                                 void* output, int block_begin, int block_end, bagua_stream_t stream);
+int bagua_mxfp4_reduce_requantize_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                        int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                        int target_chunk, int block_begin, int block_end, bagua_stream_t stream);
+
 /* MXFP4 with error feedback (MXFP4.md, "Error feedback"): the same wire format, plus
  * caller-owned f32 state, zero before the first step, that carries each step's
  * quantisation error into the next.  The state is the residual itself: worker
