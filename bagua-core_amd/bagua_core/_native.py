@@ -250,6 +250,8 @@ CORE_SIGNATURES = {
     "bagua_decentralized_low_precision_synchronous_unfused": (_i32, [_C, _T, _T, _T, _T, _i32]),
     "bagua_decentralized_low_precision_pipelined": (_i32, [_C, _T, _T, _T, _T, _i32, _i32]),
     "bagua_ring_exchange_plan": (_i32, [_i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_sz)]),
+    "bagua_centralized_piece_plan": (_i32, [_i32, _i32, _i32, _sz, _i32, _i32, _i32, ctypes.POINTER(_i32),
+                                            ctypes.POINTER(_i32), ctypes.POINTER(_sz)]),
     "bagua_bucket_create": (_vp, [ctypes.c_char_p, _T, ctypes.POINTER(ctypes.c_char_p), _i32, ctypes.POINTER(_i32)]),
     "bagua_bucket_destroy": (None, [_vp]),
     "bagua_bucket_append_op": (_i32, [_vp, ctypes.POINTER(bagua_bucket_op_t)]),

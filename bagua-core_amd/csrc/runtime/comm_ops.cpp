@@ -24,6 +24,7 @@
 #include "bagua_core.h"
 #include "comm_internal.hpp"
 #include "runtime_util.hpp"
+#include "schedule.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -71,11 +72,6 @@ struct OpTimer {
         t = now;
         return d;
     }
-};
-
-struct Chunking {
-    int p = 1, rank = 0;
-    size_t cs = 0, S = 0;
 };
 
 int plan(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int method, Chunking* k) {
@@ -154,6 +150,30 @@ int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_
 enum { kOpCentralized = 1, kOpCentralizedUnfused, kOpCentralizedPipelined, kOpOneBitPipelined, kOpRing,
        kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback, kOpMxfp4Pipelined };
 
+// The alltoall of the unpieced ops: slot j of recv <- rank j's segment `rank`.  One rank
+// receives its own bytes by a device copy (RCCL's single-rank copy kernel was slower: 1 GiB
+// op 1.257 -> 1.222 ms).
+int alltoall_or_copy(BaguaSingleCommunicatorC* c, const Chunking& k, const void* send, void* recv) {
+    if (k.p > 1) return c->t->alltoall(send, recv, k.S / k.p, BAGUA_DTYPE_U8, c->stream);
+    return hipMemcpyAsync(recv, send, k.S, hipMemcpyDeviceToDevice, c->stream) == hipSuccess ? BAGUA_OK : BAGUA_ERR_HIP;
+}
+
+// The composed middle step of an error-feedback op, for more chunks than its fused kernel
+// takes (BAGUA_ERR_UNSUPPORTED): the reference's decode + reduce into the tensor, then the
+// codec's worker encode with the server state on the own chunk alone -- compress_ef(own
+// chunk, its segment, segment bytes): one chunk, into its segment of `sb`.
+template <typename F>
+int composed_ef_middle(const bagua_tensor_t* t, int method, const Chunking& k, int average, const OpBuffer& recv,
+                       uint8_t* sb, uint64_t stream, F&& compress_ef) {
+    const bagua_tensor_t rv = u8_view(recv.ptr(), k.S, t->device_id);
+    const size_t co = k.S / k.p;
+    int rc = bagua_tensor_decompress_from(t, method, k.p, &rv, stream);
+    if (!rc) rc = bagua_tensor_reduce_inplace(t, k.p, k.rank, average, stream);
+    if (rc) return rc;
+    return compress_ef((const uint8_t*)(uintptr_t)t->ptr + (size_t)k.rank * k.cs * bagua_dtype_bytes(t->dtype),
+                       sb + (size_t)k.rank * co, co);
+}
+
 int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int method, bool fused) {
     OpTimer tm;
     double ph[5] = {0, 0, 0, 0, 0};
@@ -201,12 +221,10 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
         ph[2] = tm.lap();
         return finish(c, rc);
     }
-    // 2. (below) alltoall: slot j of recv <- rank j's segment `rank`.  One rank receives
-    // its own bytes: the MinMax steps below read them from `send` itself (their reads and
-    // the requantise's writes are separate kernels in stream order; no recv buffer), the
-    // 1-bit middle step -- one kernel that reads every segment's header while rewriting
-    // its own -- from a device copy (RCCL's single-rank copy kernel was slower: 1 GiB op
-    // 1.257 -> 1.222 ms)
+    // 2. (below) alltoall.  One rank receives its own bytes: the MinMax steps below read them
+    // from `send` itself (their reads and the requantise's writes are separate kernels in
+    // stream order; no recv buffer), the 1-bit middle step -- one kernel that reads every
+    // segment's header while rewriting its own -- from a device copy (alltoall_or_copy)
     const bool self_alias = k.p == 1 && method == BAGUA_COMPRESSION_MINMAX_UINT8;
     OpBuffer send(c), recv(c);
     TRY(send.allocate(c->device_id, k.S));
@@ -217,12 +235,7 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
     // 1. compress every chunk (target -1)
     TRY(bagua_tensor_compress_into(t, method, k.p, s, -1, &sv));
     ph[1] = tm.lap();
-    if (k.p == 1 && !self_alias)
-        TRY(hipMemcpyAsync(recv.as<void>(), send.as<void>(), k.S, hipMemcpyDeviceToDevice, c->stream) == hipSuccess
-                ? BAGUA_OK
-                : BAGUA_ERR_HIP);
-    else if (k.p > 1)
-        TRY(c->t->alltoall(send.as<void>(), recv.as<void>(), k.S / k.p, BAGUA_DTYPE_U8, c->stream));
+    if (!self_alias) TRY(alltoall_or_copy(c, k, send.as<void>(), recv.as<void>()));
     uint8_t* const rbuf = self_alias ? send.as<uint8_t>() : recv.as<uint8_t>();
     const bagua_tensor_t* const rview = self_alias ? &sv : &rv;
     // 3. reduce the p received versions of the own chunk and requantise it into send[rank]
@@ -288,52 +301,9 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
     return finish(c, BAGUA_OK);
 }
 
-// ---- pipelined centralized op ---------------------------------------------
-// The same op as above with each chunk cut into `pieces` element ranges and
-// two streams: the codec runs on the communicator's stream, the exchange of
-// piece k on a side stream while the codec works on piece k+1:
-//
-//   stream: partials | Q0 Q1 .. Qk | R0 R1 .. Rk RQ | D0 D1 .. Dk
-//   side  :             A0 A1 .. Ak            G0 G1 .. Gk
-//   (Q quantise, A alltoall as grouped send/recv, R fused dequantise+reduce,
-//    RQ requantise own chunk, G allgather, D dequantise; each arrow an event)
-//
-// A segment keeps one header per chunk and the pieces are disjoint byte ranges
-// of it, so every buffer holds exactly the bytes of the unpieced op and the
-// result is bit-identical to it (and to the reference sequence).
 int env_int(const char* name, long dflt) {
     const char* v = std::getenv(name);
     return v && *v ? (int)std::strtol(v, nullptr, 10) : (int)dflt;
-}
-
-int auto_pieces(const BaguaSingleCommunicatorC* c, size_t payload_bytes) {
-    // BAGUA_PIPELINE_PIECES caps the count (1 disables), pieces keep at least
-    // BAGUA_PIPELINE_MIN_PIECE payload bytes per chunk (= elements for MinMax
-    // u8; the exchange of a piece is p times that); both read once, at the
-    // communicator's creation (ScheduleConfig)
-    const int kmax = c->cfg.pieces_cap;
-    const int min_piece = c->cfg.min_piece;
-    size_t k = payload_bytes / (size_t)(min_piece > 0 ? min_piece : 1);
-    if (k > (size_t)kmax) k = (size_t)kmax;
-    return k < 1 ? 1 : (int)k;
-}
-
-// The op's piece schedule (bagua_kernels.h: a count, optionally OR-ed with
-// BAGUA_PIECES_TAPERED): the caller's, tapered from 3 pieces when the communicator's
-// ScheduleConfig (equal on every rank) says so -- by default the schedules the op
-// chose itself (the caller passed 0 pieces), since round 6: at the same count the
-// first piece (quantised before any byte is on the wire) and the last one (reduced and
-// dequantised after the wire) are half size, so the unhidden codec shrinks with the same
-// number of exchange groups (1 GiB fp32, 4 pieces, one GPU's kernels: prefix 208 -> 183,
-// suffix 56 -> 38 us, profiles/r06_pipe_probe_t4.json).  BAGUA_PIPELINE_TAPER=0 keeps
-// every automatic schedule uniform, =1 tapers explicit counts too.  Fixed once per op
-// and passed to every building block, so all of one op's ranges agree.
-int op_schedule(const BaguaSingleCommunicatorC* c, int count, int caller) {
-    int sched = count | (caller & BAGUA_PIECES_TAPERED);
-    const bool automatic = (caller & BAGUA_PIECES_COUNT_MASK) == 0;
-    const bool taper = c->cfg.taper > 0 || (c->cfg.taper < 0 && automatic);
-    if (count >= 3 && !(sched & BAGUA_PIECES_TAPERED) && taper) sched |= BAGUA_PIECES_TAPERED;
-    return sched;
 }
 
 // ---- BAGUA_CHECK_SCHEDULE: ranks compare what they are about to post ---------
@@ -390,19 +360,18 @@ int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_
     return BAGUA_OK;
 }
 
-bool valid_schedule(int pieces) {
-    return (pieces & ~(BAGUA_PIECES_COUNT_MASK | BAGUA_PIECES_TAPERED | BAGUA_PIECES_MULTIPATH)) == 0;
-}
-
 // Whether the op runs pipelined: every rank must decide alike (they would otherwise
 // post different collectives), so only values equal on every rank enter -- sizes,
 // dtype, p -- never this rank's pointer.  A rank whose tensor is not 16-B aligned
 // runs the same schedule on an aligned staging copy (with_aligned_copy).
-bool pipeline_fits(const BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, const Chunking& k) {
-    const size_t esz = bagua_dtype_bytes(t->dtype);
-    const size_t vec = t->dtype == BAGUA_DTYPE_F32 ? 4 : 8;  // payload bytes per 16-B vector
-    return k.p <= 16 && t->num_elem == t->num_elem_allocated && (k.S / k.p) % vec == 0 && (k.cs * esz) % 16 == 0 &&
-           c->t != nullptr;
+bool pipeline_fits(const bagua_tensor_t* t, const Chunking& k, size_t vec) {
+    // vec: the codec's vector rule -- its kernels move 16-B vectors of the tensor, so a chunk
+    // must be whole vectors and a segment whole multiples of the `vec` payload bytes one
+    // vector encodes to (0: the codec takes any chunk).  p <= 16: the fused middle steps.
+    // cs fits an int: the kernels' chunk_size (larger tensors fall back to the unpieced op,
+    // whose compress refuses them).
+    return k.p <= 16 && t->num_elem == t->num_elem_allocated && k.cs <= 0x7fffffffULL &&
+           (!vec || ((k.S / k.p) % vec == 0 && (k.cs * bagua_dtype_bytes(t->dtype)) % 16 == 0));
 }
 
 // Runs op(descriptors) on 16-B aligned copies of the tensors that are not aligned:
@@ -446,36 +415,9 @@ int with_aligned_copy(BaguaSingleCommunicatorC* c, std::vector<const bagua_tenso
     return finish(c, BAGUA_OK);
 }
 
-// bytes [lo, hi) of every segment that piece q of schedule `sched` covers: the header
-// travels with piece 0, the slack with the last non-empty piece; empty pieces move nothing
-void piece_bytes(const Chunking& k, int sched, int q, size_t* lo, size_t* hi) {
-    int b = 0, e = 0;
-    bagua_minmax_u8_piece_range((int)k.cs, sched, q, &b, &e);
-    const size_t co = k.S / k.p;
-    if (q > 0 && b == e) {
-        *lo = *hi = 0;
-        return;
-    }
-    *lo = q == 0 ? 0 : 32 + (size_t)b;
-    *hi = (size_t)e == k.cs ? co : 32 + (size_t)e;
-}
-
-// 1-bit segment bytes of tile range [tb, te): header with piece 0 when `header`, the rest
-// of the segment (slack) with the last tile
-void onebit_piece_bytes(const Chunking& k, int tb, int te, bool header, size_t* lo, size_t* hi) {
-    const size_t co = k.S / k.p;
-    const int tiles = (int)((k.cs + 1023) / 1024);
-    *lo = header ? 0 : 32 + (size_t)tb * 128;
-    *hi = te >= tiles ? co : 32 + (size_t)te * 128;
-    if (!header && tb >= te) *lo = *hi = 0;
-}
-
 // one piece of the alltoall (send -> recv) or of the in-place allgather (send): the byte
 // ranges r[0 .. nr) of every segment in one group, each pair's transfers posted in range
 // order on both ends; empty ranges move nothing
-struct ByteRange {
-    size_t lo, hi;
-};
 int exchange_ranges(BaguaSingleCommunicatorC* c, const Chunking& k, uint8_t* send, uint8_t* recv, const ByteRange* r,
                     int nr, bool alltoall) {
     bool any = false;
@@ -507,12 +449,6 @@ int exchange_ranges(BaguaSingleCommunicatorC* c, const Chunking& k, uint8_t* sen
     return rc ? rc : rc_end;
 }
 
-int exchange_piece(BaguaSingleCommunicatorC* c, const Chunking& k, uint8_t* send, uint8_t* recv, size_t lo,
-                   size_t hi, bool alltoall) {
-    const ByteRange r{lo, hi};
-    return exchange_ranges(c, k, send, recv, &r, 1, alltoall);
-}
-
 int finish_both(BaguaSingleCommunicatorC* c, int rc) {
     if (async_ops(c)) {
         // the op's stream takes over the side stream's tail: its completion is the op's
@@ -533,6 +469,42 @@ int finish_both(BaguaSingleCommunicatorC* c, int rc) {
     } while (0)
 #define HIP2(x) TRY2((x) == hipSuccess ? BAGUA_OK : BAGUA_ERR_HIP)
 
+// What every pipelined body does between its preparation and its first kernel.  Before: the
+// side stream and the op's events (ensure_side: those the op carves up and one more, the
+// last, that only the fork uses), the piece table, buffers and workspace; a failure there
+// returns through finish.  fork_side: the side stream starts after everything already
+// queued on the op's stream; from here on a failure returns through finish_both.
+int fork_side(BaguaSingleCommunicatorC* c, hipEvent_t start) {
+    if (hipEventRecord(start, c->stream) != hipSuccess) return BAGUA_ERR_HIP;
+    return hipStreamWaitEvent(c->side, start, 0) == hipSuccess ? BAGUA_OK : BAGUA_ERR_HIP;
+}
+
+// The side stream's part of one phase of an op whose pieces are exchanged one by one: piece
+// q's group once ready[q] is recorded on the op's stream, then done[q] for its consumer.
+int exchange_pieces(BaguaSingleCommunicatorC* c, const Chunking& k, uint8_t* sb, uint8_t* rb,
+                    const std::vector<Piece>& tab, bool alltoall, hipEvent_t* ready, hipEvent_t* done) {
+    for (size_t q = 0; q < tab.size(); ++q) {
+        if (hipStreamWaitEvent(c->side, ready[q], 0) != hipSuccess) return BAGUA_ERR_HIP;
+        const int rc = exchange_ranges(c, k, sb, rb, alltoall ? tab[q].a2a : tab[q].ag, 2, alltoall);
+        if (rc) return rc;
+        if (hipEventRecord(done[q], c->side) != hipSuccess) return BAGUA_ERR_HIP;
+    }
+    return BAGUA_OK;
+}
+
+// ---- pipelined centralized op ---------------------------------------------
+// The same op as above with each chunk cut into `pieces` element ranges and
+// two streams: the codec runs on the communicator's stream, the exchange of
+// piece k on a side stream while the codec works on piece k+1:
+//
+//   stream: partials | Q0 Q1 .. Qk | R0 R1 .. Rk RQ | D0 D1 .. Dk
+//   side  :             A0 A1 .. Ak            G0 G1 .. Gk
+//   (Q quantise, A alltoall as grouped send/recv, R fused dequantise+reduce,
+//    RQ requantise own chunk, G allgather, D dequantise; each arrow an event)
+//
+// A segment keeps one header per chunk and the pieces are disjoint byte ranges
+// of it, so every buffer holds exactly the bytes of the unpieced op and the
+// result is bit-identical to it (and to the reference sequence).
 int centralized_pipelined(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int pieces) {
     Chunking k;
     if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
@@ -540,23 +512,25 @@ int centralized_pipelined(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
     if (rc) return rc;
     const int caller = pieces;
     pieces &= BAGUA_PIECES_COUNT_MASK;
-    if (pieces < 1) pieces = k.p == 1 ? 1 : auto_pieces(c, k.cs);  // one rank: no exchange to hide
-    if (pieces == 1 || !pipeline_fits(c, t, k)) return centralized(c, t, average, BAGUA_COMPRESSION_MINMAX_UINT8, true);
+    if (pieces < 1) pieces = k.p == 1 ? 1 : auto_pieces(c->cfg, k.cs);  // one rank: no exchange to hide
+    const size_t vec = t->dtype == BAGUA_DTYPE_F32 ? 4 : 8;  // payload bytes per 16-B vector
+    if (pieces == 1 || !pipeline_fits(t, k, vec)) return centralized(c, t, average, BAGUA_COMPRESSION_MINMAX_UINT8, true);
     if (t->ptr % 16)
         return with_aligned_copy(c, {t}, [&](const std::vector<const bagua_tensor_t*>& u) {
             return centralized_pipelined(c, u[0], average, pieces | (caller & BAGUA_PIECES_TAPERED));
         });
-    const int sched = op_schedule(c, pieces, caller);
+    const int sched = op_schedule(c->cfg, pieces, caller);
     DeviceGuard guard(c->device_id);
     if ((rc = check_schedule(c, kOpCentralizedPipelined, BAGUA_COMPRESSION_MINMAX_UINT8, t, k.cs, sched, average)))
         return rc;
-    if (c->ensure_side(4 * (size_t)pieces + 1)) return BAGUA_ERR_HIP;
-    hipStream_t s0 = c->stream, s1 = c->side;
+    if (c->ensure_side(4 * (size_t)pieces + 1)) return finish(c, BAGUA_ERR_HIP);
+    hipStream_t s0 = c->stream;
     hipEvent_t* quantised = c->events.data();
     hipEvent_t* exchanged = quantised + pieces;
     hipEvent_t* gathered = exchanged + pieces;
     hipEvent_t* requantised_piece = gathered + pieces;
-    hipEvent_t requantised = requantised_piece[pieces];
+    std::vector<Piece> tab;
+    TRY(minmax_pieces(k, sched, &tab));
     const int dt = t->dtype, cs = (int)k.cs, p = k.p;
     void* x = (void*)(uintptr_t)t->ptr;
     OpBuffer send(c), recv(c);
@@ -571,27 +545,18 @@ int centralized_pipelined(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
     if ((rc = stream_workspace(c->device_id, (uint64_t)(uintptr_t)s0, ws_bytes, &wsp)) != BAGUA_OK)
         return finish(c, rc);
     void* ws = (void*)(uintptr_t)wsp;
-    // the side stream starts after everything already queued on the op's stream
-    HIP2(hipEventRecord(requantised, s0));
-    HIP2(hipStreamWaitEvent(s1, requantised, 0));
+    TRY2(fork_side(c, requantised_piece[pieces]));
     // 1. min/max of every chunk, then quantise + exchange piece by piece
     // (backwards: the chunks' first pieces, quantised next, stay in the Infinity Cache)
     TRY2(bagua_minmax_u8_compress_stage(env_int("BAGUA_PARTIALS_FORWARD", 0) ? 1 : 5, dt, x, (int)t->num_elem, cs, p,
                                         sb, k.S, ws, ws_bytes, -1, s0));
     for (int q = 0; q < pieces; ++q) {
-        int b, e;
-        bagua_minmax_u8_piece_range(cs, sched, q, &b, &e);
+        const int b = tab[q].b, e = tab[q].e;
         if (q == 0 || b < e)
             TRY2(bagua_minmax_u8_quantize_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, ws, ws_bytes, -1, b, e, s0));
         HIP2(hipEventRecord(quantised[q], s0));
     }
-    for (int q = 0; q < pieces; ++q) {
-        size_t lo, hi;
-        piece_bytes(k, sched, q, &lo, &hi);
-        HIP2(hipStreamWaitEvent(s1, quantised[q], 0));
-        TRY2(exchange_piece(c, k, sb, rb, lo, hi, true));
-        HIP2(hipEventRecord(exchanged[q], s1));
-    }
+    TRY2(exchange_pieces(c, k, sb, rb, tab, true, quantised, exchanged));
     // 2. reduce the p received versions of the own chunk piece by piece, requantise it.
     // The reduced chunk need not be stored (the final dequantise rewrites the own chunk
     // of x): with `recompute` each reduce piece emits its min/max partials only and the
@@ -631,18 +596,11 @@ int centralized_pipelined(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
         HIP2(hipEventRecord(requantised_piece[q], s0));
     }
     // 3. allgather + dequantise piece by piece
+    TRY2(exchange_pieces(c, k, sb, rb, tab, false, requantised_piece, gathered));
     for (int q = 0; q < pieces; ++q) {
-        size_t lo, hi;
-        piece_bytes(k, sched, q, &lo, &hi);
-        HIP2(hipStreamWaitEvent(s1, requantised_piece[q], 0));
-        TRY2(exchange_piece(c, k, sb, rb, lo, hi, false));
-        HIP2(hipEventRecord(gathered[q], s1));
-    }
-    for (int q = 0; q < pieces; ++q) {
-        int b, e;
-        bagua_minmax_u8_piece_range(cs, sched, q, &b, &e);
         HIP2(hipStreamWaitEvent(s0, gathered[q], 0));
-        if (b < e) TRY2(bagua_minmax_u8_decompress_range(dt, sb, k.S, cs, p, x, b, e, s0));
+        if (tab[q].b < tab[q].e)
+            TRY2(bagua_minmax_u8_decompress_range(dt, sb, k.S, cs, p, x, tab[q].b, tab[q].e, s0));
     }
     return finish_both(c, BAGUA_OK);
 }
@@ -656,23 +614,29 @@ int centralized_pipelined(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
 //
 //   stream: E0 E1 .. Ek F | R+F | D0 D1 .. Dk
 //   side  :    A0 A1 .. Ak+hdr   G0+hdr G1 .. Gk
-int centralized_pipelined_onebit(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int pieces) {
-    Chunking k;
-    if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
-    int rc = plan(c, t, BAGUA_COMPRESSION_ONEBIT, &k);
-    if (rc) return rc;
-    pieces &= BAGUA_PIECES_COUNT_MASK;  // 1-bit pieces are tile ranges: no tapered schedule
-    if (pieces < 1) pieces = k.p == 1 ? 1 : auto_pieces(c, k.cs / 8);  // sign bits per chunk
-    if (pieces == 1 || k.p > 16 || t->num_elem != t->num_elem_allocated || k.cs > 0x7fffffffULL)
-        return centralized(c, t, average, BAGUA_COMPRESSION_ONEBIT, true);
-    DeviceGuard guard(c->device_id);
-    if ((rc = check_schedule(c, kOpOneBitPipelined, BAGUA_COMPRESSION_ONEBIT, t, k.cs, pieces, average))) return rc;
-    if (c->ensure_side(2 * (size_t)pieces + 2)) return BAGUA_ERR_HIP;
+//
+// The same schedule runs the op with error feedback when `st` is given: E, F
+// and R+F are then the `_ef` kernels.  The worker state (carry, one scale per chunk)
+// compensates what this rank encodes for the alltoall, the server state (carry of
+// the own chunk, one scale) what it re-encodes for the allgather; alltoall,
+// allgather, final decode and segment sizes are the plain op's.  Each piece's encode
+// reads the worker scales that the step's one finalize (after the last piece, same
+// stream) then overwrites.
+struct EfState {
+    float *wc, *ws, *sc, *ss;
+};
+
+int onebit_schedule(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, const Chunking& k, int pieces,
+                    const EfState* st) {
+    int rc;
+    if (c->ensure_side(2 * (size_t)pieces + 3)) return finish(c, BAGUA_ERR_HIP);
     hipStream_t s0 = c->stream, s1 = c->side;
     hipEvent_t* encoded = c->events.data();
     hipEvent_t* gathered = encoded + pieces;
     hipEvent_t exchanged = gathered[pieces], requantised = gathered[pieces + 1];
-    const int dt = t->dtype, cs = (int)k.cs, p = k.p;
+    std::vector<Piece> tab;
+    TRY(onebit_pieces(k, pieces, &tab));
+    const int dt = t->dtype, cs = (int)k.cs, p = k.p, n = (int)t->num_elem;
     void* x = (void*)(uintptr_t)t->ptr;
     OpBuffer send(c), recv(c);
     TRY(send.allocate(c->device_id, k.S));
@@ -684,64 +648,69 @@ int centralized_pipelined_onebit(BaguaSingleCommunicatorC* c, const bagua_tensor
     if ((rc = stream_workspace(c->device_id, (uint64_t)(uintptr_t)s0, ws_bytes, &wsp)) != BAGUA_OK)
         return finish(c, rc);
     void* ws = (void*)(uintptr_t)wsp;
-    HIP2(hipEventRecord(requantised, s0));
-    HIP2(hipStreamWaitEvent(s1, requantised, 0));
-    // 1. encode piece by piece (bits + partials of every chunk), headers last
+    TRY2(fork_side(c, gathered[pieces + 2]));
+    // 1. (compensate +) encode piece by piece (bits + partials of every chunk; the carry in
+    // place), headers (and the new worker scales) last
     for (int q = 0; q < pieces; ++q) {
-        int tb, te;
-        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
-        if (te > tb) TRY2(bagua_onebit_encode_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, ws, ws_bytes, tb, te, s0));
-        if (q == pieces - 1) TRY2(bagua_onebit_finalize(ws, ws_bytes, (int)t->num_elem, cs, p, sb, k.S, s0));
+        const int tb = tab[q].b, te = tab[q].e;
+        if (te > tb)
+            TRY2(st ? bagua_onebit_encode_range_ef(dt, x, n, cs, p, sb, k.S, ws, ws_bytes, tb, te, st->wc, st->ws, s0)
+                    : bagua_onebit_encode_range(dt, x, n, cs, p, sb, k.S, ws, ws_bytes, tb, te, s0));
+        if (q == pieces - 1)
+            TRY2(st ? bagua_onebit_finalize_ef(ws, ws_bytes, n, cs, p, sb, k.S, st->ws, s0)
+                    : bagua_onebit_finalize(ws, ws_bytes, n, cs, p, sb, k.S, s0));
         HIP2(hipEventRecord(encoded[q], s0));
     }
     for (int q = 0; q < pieces; ++q) {
-        int tb, te;
-        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
-        size_t lo, hi;
-        onebit_piece_bytes(k, tb, te, false, &lo, &hi);
         HIP2(hipStreamWaitEvent(s1, encoded[q], 0));
-        TRY2(exchange_piece(c, k, sb, rb, lo, hi, true));
-        if (q == pieces - 1) TRY2(exchange_piece(c, k, sb, rb, 0, 32, true));  // the headers
+        // a group per range: the last piece's payload, then the headers
+        for (const ByteRange& r : tab[q].a2a) TRY2(exchange_ranges(c, k, sb, rb, &r, 1, true));
     }
     HIP2(hipEventRecord(exchanged, s1));
-    // 2. decode the p received segments of the own chunk, reduce, re-encode it (not stored)
+    // 2. decode the p received segments of the own chunk, reduce, (compensate with the
+    // server state,) re-encode it (the reduced chunk is not stored)
     HIP2(hipStreamWaitEvent(s0, exchanged, 0));
-    TRY2(bagua_onebit_reduce_requantize(dt, rb, k.S, cs, p, nullptr, average, sb, k.S, k.rank, ws, ws_bytes, s0));
+    if (!st) {
+        rc = bagua_onebit_reduce_requantize(dt, rb, k.S, cs, p, nullptr, average, sb, k.S, k.rank, ws, ws_bytes, s0);
+    } else {
+        rc = bagua_onebit_reduce_requantize_ef(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, ws, ws_bytes, st->sc, st->ss,
+                                               s0);
+        if (rc == BAGUA_ERR_UNSUPPORTED)
+            rc = composed_ef_middle(t, BAGUA_COMPRESSION_ONEBIT, k, average, recv, sb, (uint64_t)(uintptr_t)s0,
+                                    [&](const void* own, uint8_t* seg, size_t co) {
+                                        return bagua_onebit_compress_ef(dt, own, cs, cs, 1, seg, co, ws, ws_bytes, -1,
+                                                                        st->sc, st->ss, s0);
+                                    });
+    }
+    TRY2(rc);
     HIP2(hipEventRecord(requantised, s0));
     // 3. allgather (headers with piece 0) + decode piece by piece
     HIP2(hipStreamWaitEvent(s1, requantised, 0));
     for (int q = 0; q < pieces; ++q) {
-        int tb, te;
-        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
-        size_t lo, hi;
-        onebit_piece_bytes(k, tb, te, q == 0, &lo, &hi);
-        TRY2(exchange_piece(c, k, sb, rb, lo, hi, false));
+        TRY2(exchange_ranges(c, k, sb, rb, tab[q].ag, 2, false));
         HIP2(hipEventRecord(gathered[q], s1));
     }
     for (int q = 0; q < pieces; ++q) {
-        int tb, te;
-        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
         HIP2(hipStreamWaitEvent(s0, gathered[q], 0));
-        if (te > tb) TRY2(bagua_onebit_decompress_range(dt, sb, k.S, cs, p, x, tb, te, s0));
+        if (tab[q].e > tab[q].b) TRY2(bagua_onebit_decompress_range(dt, sb, k.S, cs, p, x, tab[q].b, tab[q].e, s0));
     }
     return finish_both(c, BAGUA_OK);
 }
 
-// The 1-bit op with error feedback: centralized_pipelined_onebit's
-// structure with the `_ef` kernels.  The worker state (carry, one scale per chunk)
-// compensates what this rank encodes for the alltoall, the server state (carry of
-// the own chunk, one scale) what it re-encodes for the allgather; alltoall,
-// allgather, final decode and segment sizes are the plain op's.  Every piece count
-// -- one included, and one rank -- takes this one path:
-//
-//   stream: E0 E1 .. Ek F | R+F | D0 D1 .. Dk        (E, F, R+F: the _ef kernels)
-//   side  :    A0 A1 .. Ak+hdr   G0+hdr G1 .. Gk
-//
-// Each piece's encode reads the worker scales that the step's one finalize (after
-// the last piece, same stream) then overwrites.
-struct EfState {
-    float *wc, *ws, *sc, *ss;
-};
+// The plain 1-bit op: pieced where every rank can tell that it fits, else unpieced.  An
+// unaligned tensor runs as it is.
+int centralized_pipelined_onebit(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int pieces) {
+    Chunking k;
+    if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
+    int rc = plan(c, t, BAGUA_COMPRESSION_ONEBIT, &k);
+    if (rc) return rc;
+    pieces &= BAGUA_PIECES_COUNT_MASK;  // 1-bit pieces are tile ranges: no tapered schedule
+    if (pieces < 1) pieces = k.p == 1 ? 1 : auto_pieces(c->cfg, k.cs / 8);  // sign bits per chunk
+    if (pieces == 1 || !pipeline_fits(t, k, 0)) return centralized(c, t, average, BAGUA_COMPRESSION_ONEBIT, true);
+    DeviceGuard guard(c->device_id);
+    if ((rc = check_schedule(c, kOpOneBitPipelined, BAGUA_COMPRESSION_ONEBIT, t, k.cs, pieces, average))) return rc;
+    return onebit_schedule(c, t, average, k, pieces, nullptr);
+}
 
 // a state tensor: F32, on the op's device, exactly `n` elements, 16-B aligned
 int ef_tensor(const bagua_tensor_t* s, uint64_t n, int device, float** out) {
@@ -752,6 +721,8 @@ int ef_tensor(const bagua_tensor_t* s, uint64_t n, int device, float** out) {
     return BAGUA_OK;
 }
 
+// The 1-bit op with error feedback (validated by its C entry): every piece count -- one
+// included, and one rank -- takes the one schedule above.
 int centralized_onebit_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, const EfState& st,
                           int pieces) {
     Chunking k;
@@ -759,8 +730,9 @@ int centralized_onebit_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
     if (rc) return rc;
     const int caller = pieces;
     pieces &= BAGUA_PIECES_COUNT_MASK;  // 1-bit pieces are tile ranges: no tapered schedule
-    if (pieces < 1) pieces = k.p == 1 ? 1 : auto_pieces(c, k.cs / 8);  // sign bits per chunk
-    if (k.p > 16) pieces = 1;  // the composed middle step reads the whole tensor
+    if (pieces < 1) pieces = k.p == 1 ? 1 : auto_pieces(c->cfg, k.cs / 8);  // sign bits per chunk
+    // (the entry admits fully valid tensors of at most INT_MAX elements only: this is p > 16)
+    if (!pipeline_fits(t, k, 0)) pieces = 1;  // the composed middle step reads the whole tensor
     if (t->ptr % 16)
         // the caller's value, not the resolved count: ranks whose alignment differs
         // resolve it from the same input and build the same piece ranges
@@ -769,80 +741,7 @@ int centralized_onebit_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
         });
     DeviceGuard guard(c->device_id);
     if ((rc = check_schedule(c, kOpOneBitErrorFeedback, BAGUA_COMPRESSION_ONEBIT, t, k.cs, pieces, average))) return rc;
-    if (c->ensure_side(2 * (size_t)pieces + 2)) return BAGUA_ERR_HIP;
-    hipStream_t s0 = c->stream, s1 = c->side;
-    hipEvent_t* encoded = c->events.data();
-    hipEvent_t* gathered = encoded + pieces;
-    hipEvent_t exchanged = gathered[pieces], requantised = gathered[pieces + 1];
-    const int dt = t->dtype, cs = (int)k.cs, p = k.p;
-    void* x = (void*)(uintptr_t)t->ptr;
-    OpBuffer send(c), recv(c);
-    TRY(send.allocate(c->device_id, k.S));
-    TRY(recv.allocate(c->device_id, k.S));
-    uint8_t* sb = send.as<uint8_t>();
-    uint8_t* rb = recv.as<uint8_t>();
-    const size_t ws_bytes = bagua_onebit_workspace_bytes(cs, p);
-    uint64_t wsp = 0;
-    if ((rc = stream_workspace(c->device_id, (uint64_t)(uintptr_t)s0, ws_bytes, &wsp)) != BAGUA_OK)
-        return finish(c, rc);
-    void* ws = (void*)(uintptr_t)wsp;
-    HIP2(hipEventRecord(requantised, s0));
-    HIP2(hipStreamWaitEvent(s1, requantised, 0));
-    // 1. compensate + encode piece by piece (bits + partials of every chunk, carry in
-    // place), headers and the new worker scales last
-    for (int q = 0; q < pieces; ++q) {
-        int tb, te;
-        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
-        if (te > tb)
-            TRY2(bagua_onebit_encode_range_ef(dt, x, (int)t->num_elem, cs, p, sb, k.S, ws, ws_bytes, tb, te, st.wc, st.ws,
-                                              s0));
-        if (q == pieces - 1)
-            TRY2(bagua_onebit_finalize_ef(ws, ws_bytes, (int)t->num_elem, cs, p, sb, k.S, st.ws, s0));
-        HIP2(hipEventRecord(encoded[q], s0));
-    }
-    for (int q = 0; q < pieces; ++q) {
-        int tb, te;
-        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
-        size_t lo, hi;
-        onebit_piece_bytes(k, tb, te, false, &lo, &hi);
-        HIP2(hipStreamWaitEvent(s1, encoded[q], 0));
-        TRY2(exchange_piece(c, k, sb, rb, lo, hi, true));
-        if (q == pieces - 1) TRY2(exchange_piece(c, k, sb, rb, 0, 32, true));  // the headers
-    }
-    HIP2(hipEventRecord(exchanged, s1));
-    // 2. decode the p received segments of the own chunk, reduce, compensate with the
-    // server state, re-encode (the reduced chunk is not stored)
-    HIP2(hipStreamWaitEvent(s0, exchanged, 0));
-    rc = bagua_onebit_reduce_requantize_ef(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, ws, ws_bytes, st.sc, st.ss, s0);
-    if (rc == BAGUA_ERR_UNSUPPORTED) {
-        // more chunks than the fused kernel takes: the reference's decode + reduce into the
-        // tensor, then the worker encode on the own chunk alone (one chunk, into its segment)
-        const bagua_tensor_t rv = u8_view(recv.ptr(), k.S, c->device_id);
-        const size_t co = k.S / k.p;
-        TRY2(bagua_tensor_decompress_from(t, BAGUA_COMPRESSION_ONEBIT, p, &rv, (uint64_t)(uintptr_t)s0));
-        TRY2(bagua_tensor_reduce_inplace(t, p, k.rank, average, (uint64_t)(uintptr_t)s0));
-        rc = bagua_onebit_compress_ef(dt, (const uint8_t*)x + (size_t)k.rank * k.cs * bagua_dtype_bytes(dt), cs, cs, 1,
-                                      sb + (size_t)k.rank * co, co, ws, ws_bytes, -1, st.sc, st.ss, s0);
-    }
-    TRY2(rc);
-    HIP2(hipEventRecord(requantised, s0));
-    // 3. allgather (headers with piece 0) + decode piece by piece
-    HIP2(hipStreamWaitEvent(s1, requantised, 0));
-    for (int q = 0; q < pieces; ++q) {
-        int tb, te;
-        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
-        size_t lo, hi;
-        onebit_piece_bytes(k, tb, te, q == 0, &lo, &hi);
-        TRY2(exchange_piece(c, k, sb, rb, lo, hi, false));
-        HIP2(hipEventRecord(gathered[q], s1));
-    }
-    for (int q = 0; q < pieces; ++q) {
-        int tb, te;
-        bagua_onebit_piece_range(cs, pieces, q, &tb, &te);
-        HIP2(hipStreamWaitEvent(s0, gathered[q], 0));
-        if (te > tb) TRY2(bagua_onebit_decompress_range(dt, sb, k.S, cs, p, x, tb, te, s0));
-    }
-    return finish_both(c, BAGUA_OK);
+    return onebit_schedule(c, t, average, k, pieces, &st);
 }
 
 // The MXFP4 op, pipelined (MXFP4.md, "Pipelined op").  Every 32-element block carries its
@@ -858,15 +757,6 @@ int centralized_onebit_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
 //   (E encode piece q of all chunks, A its alltoall, M the fused middle step on piece q of
 //    the own chunk, G its allgather, D decode piece q of all chunks; M_q waits for A_q
 //    only, G_q for M_q, D_q for G_q; the side stream posts A0 .. Ak, then G0 .. Gk)
-void mxfp4_piece_bytes(const Chunking& k, int bb, int be, ByteRange (&r)[2]) {
-    const size_t nb = (k.cs + 31) / 32, sbytes = (nb + 31) / 32 * 32, co = k.S / k.p;
-    r[0] = r[1] = ByteRange{0, 0};
-    if (bb >= be) return;
-    const bool last = (size_t)be == nb;
-    r[0] = ByteRange{(size_t)bb, last ? sbytes : (size_t)be};
-    r[1] = ByteRange{sbytes + 16 * (size_t)bb, last ? co : sbytes + 16 * (size_t)be};
-}
-
 int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int pieces) {
     Chunking k;
     if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
@@ -874,26 +764,26 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
     if (rc) return rc;
     const int caller = pieces;
     pieces &= BAGUA_PIECES_COUNT_MASK;
-    if (pieces < 1) pieces = k.p == 1 ? 1 : auto_pieces(c, k.S / k.p);  // segment bytes per chunk
+    if (pieces < 1) pieces = k.p == 1 ? 1 : auto_pieces(c->cfg, k.S / k.p);  // segment bytes per chunk
     // unpieced: one rank (no exchange to hide) and the shapes the fused middle step or the
     // vector paths cannot take -- decided from values equal on every rank only
-    if (pieces == 1 || k.p == 1 || k.p > 16 || t->num_elem != t->num_elem_allocated || k.cs > 0x7fffffffULL ||
-        (k.cs * bagua_dtype_bytes(t->dtype)) % 16)
-        return centralized(c, t, average, BAGUA_COMPRESSION_MXFP4, true);
+    // (vec = 1: a segment is whole 32-B lines, only the chunk has to be whole 16-B vectors)
+    if (pieces == 1 || k.p == 1 || !pipeline_fits(t, k, 1)) return centralized(c, t, average, BAGUA_COMPRESSION_MXFP4, true);
     if (t->ptr % 16)  // this rank alone: the same schedule on an aligned staging copy
         return with_aligned_copy(c, {t}, [&](const std::vector<const bagua_tensor_t*>& u) {
             return centralized_pipelined_mxfp4(c, u[0], average, caller);
         });
-    const int sched = op_schedule(c, pieces, caller);
+    const int sched = op_schedule(c->cfg, pieces, caller);
     DeviceGuard guard(c->device_id);
     if ((rc = check_schedule(c, kOpMxfp4Pipelined, BAGUA_COMPRESSION_MXFP4, t, k.cs, sched, average))) return rc;
-    if (c->ensure_side(4 * (size_t)pieces + 1)) return BAGUA_ERR_HIP;
-    hipStream_t s0 = c->stream, s1 = c->side;
+    if (c->ensure_side(4 * (size_t)pieces + 1)) return finish(c, BAGUA_ERR_HIP);
+    hipStream_t s0 = c->stream;
     hipEvent_t* encoded = c->events.data();
     hipEvent_t* exchanged = encoded + pieces;
     hipEvent_t* requantised = exchanged + pieces;
     hipEvent_t* gathered = requantised + pieces;
-    hipEvent_t start = gathered[pieces];
+    std::vector<Piece> tab;
+    TRY(mxfp4_pieces(k, sched, &tab));
     const int dt = t->dtype, cs = (int)k.cs, p = k.p;
     void* x = (void*)(uintptr_t)t->ptr;
     OpBuffer send(c), recv(c);
@@ -901,43 +791,29 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
     TRY(recv.allocate(c->device_id, k.S));
     uint8_t* sb = send.as<uint8_t>();
     uint8_t* rb = recv.as<uint8_t>();
-    std::vector<int> bb(pieces), be(pieces);
-    for (int q = 0; q < pieces; ++q) TRY(bagua_mxfp4_piece_range(cs, sched, q, &bb[q], &be[q]));
-    ByteRange r[2];
-    // the side stream starts after everything already queued on the op's stream
-    HIP2(hipEventRecord(start, s0));
-    HIP2(hipStreamWaitEvent(s1, start, 0));
+    TRY2(fork_side(c, gathered[pieces]));
     // 1. encode + alltoall piece by piece (an empty piece launches and moves nothing, its
     // events are recorded all the same)
     for (int q = 0; q < pieces; ++q) {
-        if (bb[q] < be[q])
-            TRY2(bagua_mxfp4_compress_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, bb[q], be[q], s0));
+        if (tab[q].b < tab[q].e)
+            TRY2(bagua_mxfp4_compress_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, tab[q].b, tab[q].e, s0));
         HIP2(hipEventRecord(encoded[q], s0));
     }
-    for (int q = 0; q < pieces; ++q) {
-        mxfp4_piece_bytes(k, bb[q], be[q], r);
-        HIP2(hipStreamWaitEvent(s1, encoded[q], 0));
-        TRY2(exchange_ranges(c, k, sb, rb, r, 2, true));
-        HIP2(hipEventRecord(exchanged[q], s1));
-    }
+    TRY2(exchange_pieces(c, k, sb, rb, tab, true, encoded, exchanged));
     // 2. the middle step of piece q as soon as it has arrived: decode the p received versions,
     // reduce, re-encode into the own segment (the reduced chunk is not stored)
     for (int q = 0; q < pieces; ++q) {
         HIP2(hipStreamWaitEvent(s0, exchanged[q], 0));
-        if (bb[q] < be[q])
-            TRY2(bagua_mxfp4_reduce_requantize_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, bb[q], be[q], s0));
+        if (tab[q].b < tab[q].e)
+            TRY2(bagua_mxfp4_reduce_requantize_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, tab[q].b, tab[q].e,
+                                                     s0));
         HIP2(hipEventRecord(requantised[q], s0));
     }
     // 3. allgather + decode piece by piece
-    for (int q = 0; q < pieces; ++q) {
-        mxfp4_piece_bytes(k, bb[q], be[q], r);
-        HIP2(hipStreamWaitEvent(s1, requantised[q], 0));
-        TRY2(exchange_ranges(c, k, sb, rb, r, 2, false));
-        HIP2(hipEventRecord(gathered[q], s1));
-    }
+    TRY2(exchange_pieces(c, k, sb, rb, tab, false, requantised, gathered));
     for (int q = 0; q < pieces; ++q) {
         HIP2(hipStreamWaitEvent(s0, gathered[q], 0));
-        if (bb[q] < be[q]) TRY2(bagua_mxfp4_decompress_range(dt, sb, k.S, cs, p, x, bb[q], be[q], s0));
+        if (tab[q].b < tab[q].e) TRY2(bagua_mxfp4_decompress_range(dt, sb, k.S, cs, p, x, tab[q].b, tab[q].e, s0));
     }
     return finish_both(c, BAGUA_OK);
 }
@@ -965,164 +841,25 @@ int centralized_mxfp4_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, i
     TRY(send.allocate(c->device_id, k.S));
     TRY(recv.allocate(c->device_id, k.S));
     const bagua_tensor_t sv = u8_view(send.ptr(), k.S, c->device_id);
-    const bagua_tensor_t rv = u8_view(recv.ptr(), k.S, c->device_id);
     // 1. compensate + encode every chunk (worker residual in place)
     TRY(bagua_mxfp4_compress_ef(dt, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, cs, p, send.as<uint8_t>(), k.S, -1,
                                 worker, sp));
     // 2. alltoall: slot j of recv <- rank j's segment `rank`
-    if (p == 1)
-        TRY(hipMemcpyAsync(recv.as<void>(), send.as<void>(), k.S, hipMemcpyDeviceToDevice, c->stream) == hipSuccess
-                ? BAGUA_OK
-                : BAGUA_ERR_HIP);
-    else
-        TRY(c->t->alltoall(send.as<void>(), recv.as<void>(), k.S / k.p, BAGUA_DTYPE_U8, c->stream));
+    TRY(alltoall_or_copy(c, k, send.as<void>(), recv.as<void>()));
     // 3. decode the p received versions of the own chunk, reduce, compensate with the server
     // residual, re-encode into send[rank] (the reduced chunk is not stored)
     rc = bagua_mxfp4_reduce_requantize_ef(dt, recv.as<uint8_t>(), k.S, cs, p, average, send.as<uint8_t>(), k.S, k.rank,
                                           server, sp);
-    if (rc == BAGUA_ERR_UNSUPPORTED) {
-        // more chunks than the fused kernel takes: decode + reduce into the tensor, then the
-        // worker encode on the own chunk alone (one chunk, into its segment)
-        const size_t co = k.S / k.p;
-        TRY(bagua_tensor_decompress_from(t, BAGUA_COMPRESSION_MXFP4, p, &rv, s));
-        TRY(bagua_tensor_reduce_inplace(t, p, k.rank, average, s));
-        rc = bagua_mxfp4_compress_ef(dt, (const uint8_t*)(uintptr_t)t->ptr + (size_t)k.rank * k.cs * bagua_dtype_bytes(dt),
-                                     cs, cs, 1, send.as<uint8_t>() + (size_t)k.rank * co, co, -1, server, sp);
-    }
+    if (rc == BAGUA_ERR_UNSUPPORTED)
+        rc = composed_ef_middle(t, BAGUA_COMPRESSION_MXFP4, k, average, recv, send.as<uint8_t>(), s,
+                                [&](const void* own, uint8_t* seg, size_t co) {
+                                    return bagua_mxfp4_compress_ef(dt, own, cs, cs, 1, seg, co, -1, server, sp);
+                                });
     TRY(rc);
     // 4. allgather the requantised chunks in place, 5. decode everything
     if (p > 1) TRY(bagua_comm_allgather_inplace(c, &sv));
     TRY(bagua_tensor_decompress_from(t, BAGUA_COMPRESSION_MXFP4, p, &sv, s));
     return finish(c, BAGUA_OK);
-}
-
-// ---- ring exchange schedule ------------------------------------------------
-// The reference sends the whole compressed bucket straight to both ring peers
-// (decentralized_low_precision_synchronous.rs:98-115).  On a fully connected
-// xGMI node that loads 2 of each GPU's 7 links and leaves 5 idle.  From 6
-// ranks on, each piece's bytes are cut into p slices: slices 0..2 go straight
-// to the peer, slice k >= 3 is sent to relay rank r + (k-1) (for the right
-// peer; r - (k-1) for the left one), which forwards it in the next group.
-// Per directed link offset o the load is then (a = 3/p direct, b = 1/p per
-// relay): o = +-1: a + b; o = +-2: 3b; others 4b, i.e. at most 4/p of the
-// payload per link (8 ranks: 1/2) instead of all of it.  The schedule is
-// deterministic and symmetric, and every transfer carries a key (hop, flow,
-// slice) so that both ends post the transfers between two ranks in the same
-// order (NCCL matches grouped p2p in posting order per pair).
-constexpr int kRingMinMultipath = 6;
-
-struct RingPlan {
-    int p = 1, r = 0, pieces = 1, groups = 1;
-    int sched = 1;  // piece schedule (count + BAGUA_PIECES_TAPERED)
-    bool mp = false;
-    Chunking k;
-    size_t slot = 0;  // relay scratch bytes per slice
-};
-
-enum { kBufMine = 0, kBufLeft = 1, kBufRight = 2, kBufRelay = 3 };
-
-// p + 1 slice boundaries of bytes [lo, hi), inner ones on 64-B lines
-void ring_slices(size_t lo, size_t hi, int p, size_t* b) {
-    const size_t len = hi - lo;
-    b[0] = lo;
-    b[p] = hi;
-    for (int i = 1; i < p; ++i) {
-        size_t x = (lo + len * (size_t)i / (size_t)p) & ~(size_t)63;
-        if (x < b[i - 1]) x = b[i - 1];
-        b[i] = x < hi ? x : hi;
-    }
-}
-
-int ring_plan(int nranks, int rank, int chunk_size, int pieces, bool multipath, RingPlan* P) {
-    if (nranks < 1 || nranks > 64 || rank < 0 || rank >= nranks || chunk_size < 0 || !valid_schedule(pieces) ||
-        (pieces & BAGUA_PIECES_COUNT_MASK) < 1)
-        return BAGUA_ERR_INVALID_ARG;
-    P->p = nranks;
-    P->r = rank;
-    P->sched = pieces;
-    pieces &= BAGUA_PIECES_COUNT_MASK;
-    P->pieces = pieces;
-    P->mp = multipath && nranks >= kRingMinMultipath;
-    P->groups = pieces + (P->mp ? 1 : 0);
-    P->k.p = 1;
-    P->k.cs = (size_t)chunk_size;
-    P->k.S = bagua_minmax_u8_compressed_bytes(BAGUA_DTYPE_F32, chunk_size, 1);  // align32(n) + 32 for every dtype
-    P->slot = 0;
-    if (P->mp) {
-        size_t b[65];
-        for (int q = 0; q < pieces; ++q) {
-            size_t lo, hi;
-            piece_bytes(P->k, P->sched, q, &lo, &hi);
-            if (hi <= lo) continue;
-            ring_slices(lo, hi, nranks, b);
-            for (int i = 3; i < nranks; ++i)
-                if (b[i + 1] - b[i] > P->slot) P->slot = b[i + 1] - b[i];
-        }
-        P->slot = (P->slot + 63) & ~(size_t)63;
-    }
-    return BAGUA_OK;
-}
-
-size_t ring_relay_bytes(const RingPlan& P) { return P.mp ? 4 * (size_t)(P.p - 3) * P.slot : 0; }
-
-// transfers of group g: the direct slices and first hops of piece g (g < pieces),
-// the relays' second hops of piece g - 1 (multipath, g > 0)
-std::vector<bagua_p2p_op_t> ring_ops(const RingPlan& P, int g) {
-    std::vector<bagua_p2p_op_t> v;
-    const int p = P.p, r = P.r;
-    auto rk = [&](int x) { return ((x % p) + p) % p; };
-    auto key = [](int hop, int flow, int slice) { return hop * 4096 + flow * 2048 + slice; };
-    auto add = [&](int peer, int send, int buf, int k, size_t off, size_t len) {
-        if (len) v.push_back(bagua_p2p_op_t{peer, send, buf, k, (uint64_t)off, (uint64_t)len});
-    };
-    auto relay_off = [&](int q, int flow, int slice) {
-        return ((size_t)((q & 1) * 2 + flow) * (size_t)(p - 3) + (size_t)(slice - 3)) * P.slot;
-    };
-    const int left = rk(r - 1), right = rk(r + 1);
-    size_t b[65];
-    if (g < P.pieces) {
-        size_t lo, hi;
-        piece_bytes(P.k, P.sched, g, &lo, &hi);
-        if (hi > lo) {
-            const size_t dhi = P.mp ? (ring_slices(lo, hi, p, b), b[3]) : hi;
-            // flow 0: towards the right peer (lands in its left buffer); flow 1: towards the left peer
-            add(right, 1, kBufMine, key(0, 0, 0), lo, dhi - lo);
-            add(left, 1, kBufMine, key(0, 1, 0), lo, dhi - lo);
-            add(left, 0, kBufLeft, key(0, 0, 0), lo, dhi - lo);
-            add(right, 0, kBufRight, key(0, 1, 0), lo, dhi - lo);
-            if (P.mp)
-                for (int i = 3; i < p; ++i) {
-                    const int d = i - 1;
-                    const size_t len = b[i + 1] - b[i];
-                    add(rk(r + d), 1, kBufMine, key(1, 0, i), b[i], len);
-                    add(rk(r - d), 1, kBufMine, key(1, 1, i), b[i], len);
-                    add(rk(r - d), 0, kBufRelay, key(1, 0, i), relay_off(g, 0, i), len);  // source r-d's slice
-                    add(rk(r + d), 0, kBufRelay, key(1, 1, i), relay_off(g, 1, i), len);  // source r+d's slice
-                }
-        }
-    }
-    if (P.mp && g > 0) {
-        const int q = g - 1;
-        size_t lo, hi;
-        piece_bytes(P.k, P.sched, q, &lo, &hi);
-        if (hi > lo) {
-            ring_slices(lo, hi, p, b);
-            for (int i = 3; i < p; ++i) {
-                const int d = i - 1;
-                const size_t len = b[i + 1] - b[i];
-                add(rk(r - d + 1), 1, kBufRelay, key(2, 0, i), relay_off(q, 0, i), len);  // source r-d -> its right
-                add(rk(r + d - 1), 1, kBufRelay, key(2, 1, i), relay_off(q, 1, i), len);  // source r+d -> its left
-                add(rk(r + d - 1), 0, kBufLeft, key(2, 0, i), b[i], len);    // left peer's slice via (r-1)+d
-                add(rk(r - d + 1), 0, kBufRight, key(2, 1, i), b[i], len);   // right peer's slice via (r+1)-d
-            }
-        }
-    }
-    std::stable_sort(v.begin(), v.end(), [](const bagua_p2p_op_t& a, const bagua_p2p_op_t& c) {
-        if (a.peer != c.peer) return a.peer < c.peer;
-        if (a.is_send != c.is_send) return a.is_send > c.is_send;
-        return a.key < c.key;
-    });
-    return v;
 }
 
 // one group of the ring exchange on the side stream
@@ -1268,8 +1005,8 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
     // the exchange schedule, from values equal on every rank (ScheduleConfig included)
     const int caller = pieces;
     pieces &= BAGUA_PIECES_COUNT_MASK;
-    if (pieces < 1) pieces = c->nranks == 1 ? 1 : auto_pieces(c, (size_t)n);
-    const int sched = op_schedule(c, pieces, caller);
+    if (pieces < 1) pieces = c->nranks == 1 ? 1 : auto_pieces(c->cfg, (size_t)n);
+    const int sched = op_schedule(c->cfg, pieces, caller);
     const bool multipath =
         (caller & BAGUA_PIECES_MULTIPATH) ? (int)c->nranks >= kRingMinMultipath : ring_multipath_enabled(c);
     // (MXFP4 stays unpieced: one mix, one exchange, one apply, whatever the schedule asks for)
@@ -1334,16 +1071,13 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
                 hipStream_t s1 = c->side;
                 hipEvent_t* quantised = c->events.data();
                 hipEvent_t* exchanged = quantised + pieces;
-                hipEvent_t start = exchanged[pieces];
                 uint8_t* mb = mine.as<uint8_t>();
                 uint8_t* lb = lbuf.as<uint8_t>();
                 uint8_t* rb = rbuf.as<uint8_t>();
                 uint8_t* const bufs[4] = {mb, lb, rb, relay.as<uint8_t>()};
-                HIP2(hipEventRecord(start, c->stream));
-                HIP2(hipStreamWaitEvent(s1, start, 0));
+                TRY2(fork_side(c, exchanged[pieces]));
                 for (int q = 0; q < pieces; ++q) {
-                    int b, e;
-                    bagua_minmax_u8_piece_range(n, sched, q, &b, &e);
+                    const int b = plan.tab[q].b, e = plan.tab[q].e;
                     if (q == 0 || b < e)
                         TRY2(bagua_minmax_u8_quantize_range(t->dtype, tp, n, n, 1, mb, S, ws, wsb, -1, b, e, sp));
                     HIP2(hipEventRecord(quantised[q], c->stream));
@@ -1355,8 +1089,7 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
                     if (done >= 0) HIP2(hipEventRecord(exchanged[done], s1));
                 }
                 for (int q = 0; q < pieces; ++q) {
-                    int b, e;
-                    bagua_minmax_u8_piece_range(n, sched, q, &b, &e);
+                    const int b = plan.tab[q].b, e = plan.tab[q].e;
                     HIP2(hipStreamWaitEvent(c->stream, exchanged[q], 0));
                     if (b < e)
                         TRY2(bagua_ring_apply_minmax_range(t->dtype, mb, lb, rb, S, n, b, e, tp, wp, lp, rp, sp));
@@ -1415,28 +1148,6 @@ int bagua_comm_set_async(BaguaSingleCommunicatorC* c, int on) {
     if (!c) return BAGUA_ERR_INVALID_ARG;
     c->async = on != 0;
     return BAGUA_OK;
-}
-
-int bagua_ring_exchange_plan(int nranks, int rank, int chunk_size, int pieces, int multipath, int* groups,
-                             size_t* relay_bytes) {
-    RingPlan P;
-    const int rc = ring_plan(nranks, rank, chunk_size, pieces, multipath != 0, &P);
-    if (rc) return rc;
-    if (groups) *groups = P.groups;
-    if (relay_bytes) *relay_bytes = ring_relay_bytes(P);
-    return BAGUA_OK;
-}
-
-int bagua_ring_exchange_ops(int nranks, int rank, int chunk_size, int pieces, int multipath, int group,
-                            bagua_p2p_op_t* ops, int max_ops) {
-    RingPlan P;
-    const int rc = ring_plan(nranks, rank, chunk_size, pieces, multipath != 0, &P);
-    if (rc) return -rc;
-    if (group < 0 || group >= P.groups) return -BAGUA_ERR_INVALID_ARG;
-    const std::vector<bagua_p2p_op_t> v = ring_ops(P, group);
-    if (!ops || (int)v.size() > max_ops) return -BAGUA_ERR_INVALID_ARG;
-    std::copy(v.begin(), v.end(), ops);
-    return (int)v.size();
 }
 
 int bagua_decentralized_low_precision_synchronous(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t,

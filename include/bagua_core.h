@@ -263,6 +263,18 @@ int bagua_ring_exchange_plan(int nranks, int rank, int chunk_size, int pieces, i
                              size_t* relay_bytes);
 int bagua_ring_exchange_ops(int nranks, int rank, int chunk_size, int pieces, int multipath, int group,
                             bagua_p2p_op_t* ops, int max_ops);
+/* Piece table of the pipelined centralized ops (host-only, no device work, no communicator):
+ * what piece `piece` of schedule `schedule` (a count >= 1, optionally OR-ed with
+ * BAGUA_PIECES_TAPERED) covers for `method` at `nranks` chunks of `chunk_size` elements.
+ * *unit_begin / *unit_end: its unit range in every chunk (MinMax: elements, 1-bit:
+ * 1024-element tiles, MXFP4: 32-element blocks); byte_ranges[4] = {lo0, hi0, lo1, hi1}: the
+ * two byte ranges of every segment that its exchange of `phase` moves (0 alltoall, 1
+ * allgather; hi <= lo: nothing).  Per phase the non-empty ranges of all pieces partition
+ * the segment.  Returns the number of pieces, or a negative status: unknown schedule bits,
+ * no count, a piece outside the count, sizes the op refuses (-BAGUA_ERR_INVALID_ARG), a
+ * method without a pieced op (-BAGUA_ERR_UNSUPPORTED).  Any output may be NULL. */
+int bagua_centralized_piece_plan(int method, int dtype, int nranks, size_t chunk_size, int schedule, int piece,
+                                 int phase, int* unit_begin, int* unit_end, size_t* byte_ranges);
 /* Hierarchical mode (communicators/mod.rs:243-427): intranode reduce (AVG when the op
  * averages; always AVG for the decentralized op) into intranode rank 0, the op among
  * the node leaders on `internode` (needed on the leader only, same stream and device as

@@ -55,7 +55,7 @@ def _piece_range(cs: int, pieces: int, q: int) -> tuple[int, int]:
 
 
 def _piece_bytes(cs: int, co: int, pieces: int, q: int) -> tuple[int, int]:
-    # comm_ops.cpp piece_bytes: header with piece 0, slack with the last non-empty piece
+    # schedule.cpp minmax_pieces: header with piece 0, slack with the last non-empty piece
     b, e = _piece_range(cs, pieces, q)
     if q > 0 and b == e:
         return 0, 0
@@ -107,7 +107,7 @@ def centralized_pieced_rank(rank: int, world: int, port: int, inputs_path: str, 
 
 
 def _onebit_piece_bytes(cs: int, co: int, pieces: int, q: int, header: bool) -> tuple[int, int]:
-    # comm_ops.cpp onebit_piece_bytes: tile range of bagua_onebit_piece_range, 128 B per tile
+    # schedule.cpp onebit_pieces: tile range of bagua_onebit_piece_range, 128 B per tile
     import ctypes
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = ctypes.CDLL(os.path.join(root, "bagua-core_amd", "lib", "libbagua_kernels.so"))
@@ -237,7 +237,7 @@ def ring_ops(p: int, rank: int, n: int, pieces: int, multipath: bool, group: int
 
 def decentralized_multipath_rank(rank: int, world: int, port: int, inputs_path: str, out_dir: str, dtype: int,
                                  pieces: int) -> None:
-    """The fused ring op's exchange (comm_ops.cpp ring_ops: direct slices + relayed slices,
+    """The fused ring op's exchange (schedule.cpp ring_ops: direct slices + relayed slices,
     relays forward one group later) executed with gloo point-to-point transfers; a
     transfer is matched by its (hop, flow, slice) key, so the test checks the routing
     itself.  Receive buffers are poisoned: every byte must arrive."""

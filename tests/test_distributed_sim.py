@@ -130,7 +130,7 @@ def _simulate_ring_exchange(p: int, n: int, pieces: int, multipath: bool, rng) -
 @pytest.mark.parametrize("multipath", [False, True])
 @pytest.mark.parametrize("n", [200_003, 100])  # 100: slices of a few bytes, most of them empty
 def test_ring_exchange_schedule(p, pieces, multipath, n):
-    """Host-only check of the ring exchange schedule (comm_ops.cpp ring_ops): every rank
+    """Host-only check of the ring exchange schedule (schedule.cpp ring_ops): every rank
     ends with its left and right peers' payload byte for byte, matched transfers agree
     on key and size, and with multipath from 6 ranks on no link carries more than
     4/p of a payload (8 ranks: half; direct: all of it) plus slice rounding."""

@@ -394,7 +394,7 @@ def test_pipelined_ops_back_to_back_fuzz(bc, oracle_c):
                                                        (8, F32, (1 << 20) + 3, 4, True)])
 def test_decentralized_multipath_multirank(bc, oracle_c, p, dtype, n, pieces, multipath, monkeypatch):
     """Ring op with the multipath exchange (from 6 ranks: 3/p of each piece straight to the
-    peer, the other slices relayed through ranks r +- (k-1) one group later; comm_ops.cpp
+    peer, the other slices relayed through ranks r +- (k-1) one group later; schedule.cpp
     ring_ops) == the oracle's op simulation on every rank and tensor; multipath False
     (BAGUA_RING_MULTIPATH=0) is the reference's direct exchange."""
     from bagua_core.communicator import loopback_communicators
