@@ -9,12 +9,13 @@ from . import _native
 from .backend import BaguaCommBackendPy
 from .bucket import BaguaBucketPy
 from .communicator import BaguaSingleCommunicatorPy
-from .tensor import METHODS, BaguaTensorPy, MXFP4ErrorFeedbackState, OneBitErrorFeedbackState
+from .tensor import (METHODS, BaguaTensorPy, MXFP4ErrorFeedbackState, MXFP4StochasticRounding,
+                     OneBitErrorFeedbackState)
 
 __version__ = "0.1.0+mi355x"
 
 __all__ = ["BaguaCommBackendPy", "BaguaBucketPy", "BaguaSingleCommunicatorPy", "BaguaTensorPy", "METHODS",
-           "MXFP4ErrorFeedbackState", "OneBitErrorFeedbackState", "show_version"]
+           "MXFP4ErrorFeedbackState", "MXFP4StochasticRounding", "OneBitErrorFeedbackState", "show_version"]
 
 
 def show_version() -> None:

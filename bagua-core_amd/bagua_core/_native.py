@@ -58,10 +58,17 @@ class bagua_bucket_op_t(ctypes.Structure):
                 ("ef_server_carry", bagua_tensor_t), ("ef_server_scale", bagua_tensor_t)]
 
 
+class bagua_bucket_op_sr_t(bagua_bucket_op_t):
+    """the whole of include/bagua_core.h bagua_bucket_op_t: sr_seed, read for
+    BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC only, was appended to the fields above"""
+    _fields_ = [("sr_seed", ctypes.c_uint64)]
+
+
 BUCKET_OP_CENTRALIZED_LOW_PRECISION, BUCKET_OP_CENTRALIZED_FULL_PRECISION = 1, 2
 BUCKET_OP_DECENTRALIZED_LOW_PRECISION, BUCKET_OP_CALLBACK = 3, 4
 BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK = 5
 BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK = 6
+BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC = 7
 STATUS_INVALID_ARG = 1
 
 _T = ctypes.POINTER(bagua_tensor_t)
@@ -151,6 +158,13 @@ KERNEL_SIGNATURES = {
     "bagua_mxfp4_ef_state_bytes": (_i32, [_i32, _i32, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
     "bagua_mxfp4_compress_ef": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
     "bagua_mxfp4_reduce_requantize_ef": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
+    "bagua_mxfp4_sr_key": (_u64, [_u64, _u64, _i32, _i32]),
+    "bagua_mxfp4_sr_word": (ctypes.c_uint32, [_u64, ctypes.c_uint32]),
+    "bagua_mxfp4_compress_sr": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _u64, _vp]),
+    "bagua_mxfp4_compress_sr_range": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _u64, _vp]),
+    "bagua_mxfp4_reduce_requantize_sr": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _u64, _vp]),
+    "bagua_mxfp4_reduce_requantize_sr_range": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _i32,
+                                                      _u64, _vp]),
     "bagua_ring_mix_mxfp4": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "bagua_ring_apply_mxfp4": (_i32, [_i32, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp]),
     "bagua_ring_one_rank_mxfp4": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _vp]),
@@ -205,6 +219,7 @@ CORE_SIGNATURES = {
     "bagua_tensor_compress_into": (_i32, [_T, _i32, _i32, _u64, _i32, _T]),
     "bagua_tensor_compress_error_feedback": (_i32, [_T, _i32, _u64, _T, _T, _T]),
     "bagua_tensor_compress_mxfp4_error_feedback": (_i32, [_T, _i32, _u64, _T, _T]),
+    "bagua_tensor_compress_mxfp4_stochastic": (_i32, [_T, _i32, _u64, _u64, _u64, _T]),
     "bagua_tensor_decompress_from": (_i32, [_T, _i32, _i32, _T, _u64]),
     "bagua_tensor_reduce_inplace": (_i32, [_T, _i32, _i32, _i32, _u64]),
     "bagua_tensor_add_inplace": (_i32, [_T, _T, _u64]),
@@ -245,6 +260,7 @@ CORE_SIGNATURES = {
     "bagua_centralized_low_precision_pipelined": (_i32, [_C, _T, _i32, _i32, _i32]),
     "bagua_centralized_onebit_error_feedback": (_i32, [_C, _T, _i32, _T, _T, _T, _T, _i32]),
     "bagua_centralized_mxfp4_error_feedback": (_i32, [_C, _T, _i32, _T, _T]),
+    "bagua_centralized_mxfp4_stochastic": (_i32, [_C, _T, _i32, _u64, _u64, _i32]),
     "bagua_centralized_full_precision_synchronous": (_i32, [_C, _T, _i32]),
     "bagua_decentralized_low_precision_synchronous": (_i32, [_C, _T, _T, _T, _T, _i32]),
     "bagua_decentralized_low_precision_synchronous_unfused": (_i32, [_C, _T, _T, _T, _T, _i32]),

@@ -10,6 +10,7 @@ on the communicator's stream:
   CentralizedLowPrecisionSynchronous   -> bagua_centralized_low_precision_synchronous
   CentralizedOneBitErrorFeedback       -> bagua_centralized_onebit_error_feedback
   CentralizedMXFP4ErrorFeedback        -> bagua_centralized_mxfp4_error_feedback
+  CentralizedMXFP4Stochastic           -> bagua_centralized_mxfp4_stochastic
   CentralizedFullPrecisionSynchronous  -> bagua_centralized_full_precision_synchronous
   DecentralizedLowPrecisionSynchronous -> bagua_decentralized_low_precision_synchronous
   PythonOp                             -> a ctypes callback (python_ffi_op.rs)
@@ -28,7 +29,8 @@ from typing import Callable, Optional
 
 from . import _native as N
 from .communicator import BaguaSingleCommunicatorPy
-from .tensor import _DTYPES, BaguaTensorPy, MXFP4ErrorFeedbackState, OneBitErrorFeedbackState, compression_code
+from .tensor import (_DTYPES, BaguaTensorPy, MXFP4ErrorFeedbackState, MXFP4StochasticRounding,
+                     OneBitErrorFeedbackState, compression_code)
 
 CALLBACK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_char_p)
 
@@ -85,6 +87,21 @@ class CentralizedMXFP4ErrorFeedback:
                                    compression=compression_code(self.compression), fused=1,
                                    comm=_handle(self.communicator), ef_worker_carry=st._raw(st.worker_residual),
                                    ef_server_carry=st._raw(st.server_residual))
+
+
+@dataclass
+class CentralizedMXFP4Stochastic:
+    """the "MXFP4" centralized op with stochastic rounding; the native op counts its
+    executions (step 0 is the first after the append)"""
+    communicator: BaguaSingleCommunicatorPy
+    average: bool
+    rounding: MXFP4StochasticRounding
+    compression: str = "MXFP4"
+
+    def native(self) -> N.bagua_bucket_op_t:
+        return N.bagua_bucket_op_sr_t(kind=N.BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC, average=int(self.average),
+                                      compression=compression_code(self.compression), fused=1,
+                                      comm=_handle(self.communicator), sr_seed=self.rounding.seed)
 
 
 # the state class of each codec that has error feedback, and the op it appends
@@ -212,11 +229,19 @@ class BaguaBucketPy:
                                           communicator_intranode: Optional[BaguaSingleCommunicatorPy] = None,
                                           hierarchical: bool = False, average: bool = True,
                                           scattergather: bool = False, compression: Optional[str] = None,
-                                          error_feedback=None) -> None:
+                                          error_feedback=None, stochastic_rounding=None) -> None:
         """error_feedback (keyword; not hierarchical): the state that carries the op's
         quantisation error from one execution to the next -- a OneBitErrorFeedbackState with
         "OneBitSignScale", an MXFP4ErrorFeedbackState with "MXFP4".
+
+        stochastic_rounding (keyword; "MXFP4" only, not hierarchical, not together with
+        error_feedback): an MXFP4StochasticRounding.  Both encodes of the op round at random
+        with zero bias instead of to nearest; the op's n-th execution uses step n - 1.
         """
+        if stochastic_rounding is not None:
+            self._append_stochastic(communicator_internode, hierarchical, average, compression, error_feedback,
+                                    stochastic_rounding)
+            return
         if error_feedback is not None:
             self._append_error_feedback(communicator_internode, hierarchical, average, compression, error_feedback)
             return
@@ -228,6 +253,22 @@ class BaguaBucketPy:
         else:
             compression_code(compression)
             self._append(CentralizedLowPrecisionSynchronous(comm, average, compression, intranode=intra))
+
+    def _append_stochastic(self, comm, hierarchical, average, compression, error_feedback, rounding) -> None:
+        if compression != "MXFP4":
+            raise NotImplementedError(f"stochastic rounding exists for the MXFP4 codec only, not for "
+                                      f"compression={compression!r}")
+        if hierarchical:
+            raise NotImplementedError("stochastic rounding is not available in hierarchical mode")
+        if error_feedback is not None:
+            raise NotImplementedError("stochastic rounding and error feedback cannot be combined")
+        if comm is None:
+            raise RuntimeError("inter node communicator must be given in non-hierarchical mode")
+        if not isinstance(rounding, MXFP4StochasticRounding):
+            raise TypeError("stochastic_rounding must be an MXFP4StochasticRounding")
+        if self._tensors[0].raw().dtype not in (N.DTYPE_F32, N.DTYPE_F16, N.DTYPE_BF16):
+            raise RuntimeError("stochastic rounding needs a floating-point bucket")
+        self._append(CentralizedMXFP4Stochastic(comm, average, rounding))
 
     def _append_error_feedback(self, comm, hierarchical, average, compression, state) -> None:
         if compression not in _EF_CODECS:

@@ -205,6 +205,26 @@ class BaguaTensorPy:
         res._used_on(stream)
         return res
 
+    def compress_with_stochastic_rounding(self, n_chunks: int, rounding: "MXFP4StochasticRounding",
+                                          step: int) -> "BaguaTensorPy":
+        """compress("MXFP4", n_chunks, -1) with every element rounded to one of its two grid
+        neighbours at random, so that the decode's expectation is the input (MXFP4.md,
+        "Stochastic rounding").  The same (rounding.seed, step) gives the same bytes;
+        decompress_from("MXFP4", ...) decodes them.  The result is owned like compress()'s."""
+        if not isinstance(rounding, MXFP4StochasticRounding):
+            raise TypeError("rounding must be an MXFP4StochasticRounding")
+        src = self.raw()
+        if n_chunks <= 0 or src.num_elem_allocated % n_chunks != 0:
+            raise RuntimeError("compression tensor size % n_chunks must be 0")
+        out = N.bagua_tensor_t()
+        stream = current_stream_ptr(src.device_id)
+        rc = N.C.bagua_tensor_compress_mxfp4_stochastic(ctypes.byref(src), n_chunks, stream, rounding.seed,
+                                                        int(step) & _U64, ctypes.byref(out))
+        N.check(rc, f"compress_with_stochastic_rounding(n_chunks={n_chunks}, step={step})")
+        res = BaguaTensorPy._from_raw(out, "compressed_tensor", owned=True)
+        res._used_on(stream)
+        return res
+
     def decompress_from(self, method: str, n_chunks: int, compressed_buffer: "BaguaTensorPy") -> None:
         code = compression_code(method)
         dst = self.raw()
@@ -258,6 +278,23 @@ class BaguaTensorPy:
         r = self.raw()
         return (f"BaguaTensorPy(name={self._name!r}, dtype={_DTYPE_NAMES[r.dtype]}, num_elements={r.num_elem}, "
                 f"device_id={r.device_id})")
+
+
+_U64 = (1 << 64) - 1
+
+
+class MXFP4StochasticRounding:
+    """Stochastic rounding for the "MXFP4" codec (MXFP4.md): nothing but a seed, taken modulo
+    2^64.  There is no state on the device; an op that takes it counts its own executions, and
+    (seed, step, rank) decide every rounding, so a run is reproducible."""
+
+    def __init__(self, seed: int):
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise TypeError("seed must be an int")
+        self.seed = seed & _U64
+
+    def __repr__(self) -> str:
+        return f"MXFP4StochasticRounding(seed={self.seed:#x})"
 
 
 class OneBitErrorFeedbackState:

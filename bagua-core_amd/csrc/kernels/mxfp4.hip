@@ -13,7 +13,8 @@
 //            received versions eight elements at a time, sums them in the reference's
 //            tree order (reduce.hip), rounds to T and encodes the 32 results
 // and the two error-feedback kernels, the encode and the middle step with an f32 residual
-// read and rewritten in the same pass (further down).
+// read and rewritten in the same pass (further down).  SR = true on the encode and the middle
+// step rounds stochastically (MXFP4.md, "Stochastic rounding"): same data movement, mx_quant_sr.
 //
 // HW = true takes gfx950's conversions (v_cvt_scalef32_pk_fp4_f32 / _pk_f32_fp4) for the
 // rounding to and from E2M1; the scale byte, NaN blocks, the inf and largest-finite
@@ -77,10 +78,16 @@ __device__ __forceinline__ void mx_encode(const float (&x)[kMxBlock], float maxf
 // [0, nb)): bb is a multiple of kMxGranule, be another or nb, so a range starts on a wave
 // tile of every kernel and only the range that ends at nb has a ragged tile and the slack.
 // ------------------------------------------------------------------------
-template <typename T, bool HW>
+//
+// SR (MXFP4.md, "Stochastic rounding"): the same kernel with mx_quant_sr for the element
+// rounding; a lane hashes once per pair of its vector, the word's index being the pair's
+// index in the whole tensor (chunk * cs + index in chunk), so the bytes do not depend on
+// chunking, range or grid.  k0 / k1: the halves of the 64-bit key, unused otherwise.
+template <typename T, bool HW, bool SR>
 __global__ __launch_bounds__(kBlock) void mxfp4_encode_kernel(const typename T::storage* __restrict__ in,
                                                              int64_t in_num_elem, int64_t cs, int target,
-                                                             uint8_t* __restrict__ out, int64_t bb, int64_t be) {
+                                                             uint8_t* __restrict__ out, int64_t bb, int64_t be,
+                                                             uint32_t k0, uint32_t k1) {
     using S = typename T::storage;
     constexpr int N = Vec<T>::N;        // elements per 16-B vector: 4 / 8
     constexpr int G = kMxBlock / N;     // lanes per block: 8 / 4
@@ -135,7 +142,13 @@ __global__ __launch_bounds__(kBlock) void mxfp4_encode_kernel(const typename T::
             uint32_t byte = kMxNanScale, w = 0;
             if (am <= 0x7f800000u) {
                 byte = mx_scale_byte(min(am, __float_as_uint(maxf)));
-                if constexpr (HW) {
+                if constexpr (SR) {
+                    const float inv = mx_inv_scale(byte);
+                    uint32_t r[N];
+                    mx_sr_bits<N>((uint32_t)((int64_t)c * cs + (bb + b0 + k * BW) * kMxBlock + lane * N), k0, k1, r);
+#pragma unroll
+                    for (int e = 0; e < N; ++e) w |= mx_quant_sr(mx_clamp(f[k][e], maxf), inv, r[e]) << (4 * e);
+                } else if constexpr (HW) {
                     const float scale = __uint_as_float(byte << 23);
                     w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(f[k][0], maxf), mx_clamp(f[k][1], maxf), scale, 0);
                     w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(f[k][2], maxf), mx_clamp(f[k][3], maxf), scale, 1);
@@ -222,12 +235,17 @@ __global__ __launch_bounds__(kBlock) void mxfp4_decode_kernel(const uint8_t* __r
 // s[y] += s[y + h]; the mean is s / p; rounded to T) and encode the result into the own
 // segment.  Equal, byte for byte, to decompress + bagua_reduce_chunks + compress(target).
 // ------------------------------------------------------------------------
-template <typename T, int BY, bool HW, bool STORE>
+//
+// SR (never storing): the re-encode rounds stochastically, hashing with the index of the own
+// chunk's elements in the whole tensor, j = target * cs + index, as compress_sr(target) does.
+template <typename T, int BY, bool HW, bool STORE, bool SR>
 __global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_kernel(const uint8_t* __restrict__ in, int64_t cs, int p,
                                                                     int average,
                                                                     typename T::storage* __restrict__ chunk,
                                                                     uint8_t* __restrict__ out_seg, int64_t bb,
-                                                                    int64_t be) {
+                                                                    int64_t be, uint32_t j_chunk, uint32_t k0,
+                                                                    uint32_t k1) {
+    static_assert(!(SR && STORE), "the stochastic middle step does not store the reduced chunk");
     constexpr int N = Vec<T>::N;
     const int64_t nb = mx_blocks(cs), sbytes = mx_scale_bytes(cs), pbytes = mx_payload_bytes(cs);
     const int64_t segb = sbytes + pbytes;
@@ -286,7 +304,8 @@ __global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_kernel(const uint8
             }
         }
         uint32_t byte, w[4];
-        mx_encode<HW>(x, maxf, byte, w);
+        if constexpr (SR) mx_encode_block_sr(x, maxf, j_chunk + (uint32_t)b * kMxBlock, k0, k1, byte, w);
+        else mx_encode<HW>(x, maxf, byte, w);
         out_seg[b] = (uint8_t)byte;
         *reinterpret_cast<uint4*>(pay_out + b * kMxBlockBytes) = make_uint4(w[0], w[1], w[2], w[3]);
         if (b == nb - 1) {
@@ -575,7 +594,7 @@ static bool mx_range(int cs, int& bb, int& be) {
 
 template <typename T>
 static int mx_compress_impl(const void* input, int in_num_elem, int cs, int p, uint8_t* out, size_t out_bytes,
-                            int target, int bb, int be, hipStream_t s) {
+                            int target, int bb, int be, const uint64_t* key, hipStream_t s) {
     using S = typename T::storage;
     if (p <= 0 || p > 65535 || cs < 0 || in_num_elem < 0 || target < -1 || target >= p || !out || !input)
         return BAGUA_ERR_INVALID_ARG;
@@ -589,12 +608,16 @@ static int mx_compress_impl(const void* input, int in_num_elem, int cs, int p, u
     const dim3 grid(mx_grid(((int64_t)(be - bb) + kTileBlocks - 1) / kTileBlocks, kWavesPerBlock, nact,
                             "BAGUA_TUNE_MX_ENCODE_BLOCKS"),
                     nact);
-    if (mx_hw())
-        launch(mxfp4_encode_kernel<T, true>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
-               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be);
+    if (key)  // stochastic rounding: the arithmetic alone (MXFP4.md, "The hardware conversion")
+        launch(mxfp4_encode_kernel<T, false, true>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
+               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be, (uint32_t)*key,
+               (uint32_t)(*key >> 32));
+    else if (mx_hw())
+        launch(mxfp4_encode_kernel<T, true, false>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
+               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be, 0u, 0u);
     else
-        launch(mxfp4_encode_kernel<T, false>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
-               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be);
+        launch(mxfp4_encode_kernel<T, false, false>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
+               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be, 0u, 0u);
     return check_launch();
 }
 
@@ -629,28 +652,34 @@ static int mx_decompress_impl(const uint8_t* in, size_t in_bytes, int cs, int p,
 
 template <typename T, int BY, bool HW>
 static void mx_launch_reduce(int blocks, const uint8_t* in, int64_t cs, int p, int average,
-                             typename T::storage* chunk, uint8_t* seg, int64_t bb, int64_t be, hipStream_t s) {
-    if (chunk)
-        launch(mxfp4_reduce_encode_kernel<T, BY, HW, true>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average,
-               chunk, seg, bb, be);
+                             typename T::storage* chunk, uint8_t* seg, int64_t bb, int64_t be, uint32_t j_chunk,
+                             const uint64_t* key, hipStream_t s) {
+    if (key)  // stochastic re-encode (never storing); the decode of the received segments is the plain one
+        launch(mxfp4_reduce_encode_kernel<T, BY, HW, false, true>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p,
+               average, chunk, seg, bb, be, j_chunk, (uint32_t)*key, (uint32_t)(*key >> 32));
+    else if (chunk)
+        launch(mxfp4_reduce_encode_kernel<T, BY, HW, true, false>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p,
+               average, chunk, seg, bb, be, 0u, 0u, 0u);
     else
-        launch(mxfp4_reduce_encode_kernel<T, BY, HW, false>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average,
-               chunk, seg, bb, be);
+        launch(mxfp4_reduce_encode_kernel<T, BY, HW, false, false>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p,
+               average, chunk, seg, bb, be, 0u, 0u, 0u);
 }
 
 template <typename T, bool HW>
 static void mx_dispatch_reduce(int blocks, const uint8_t* in, int64_t cs, int p, int average,
-                               typename T::storage* chunk, uint8_t* seg, int64_t bb, int64_t be, hipStream_t s) {
+                               typename T::storage* chunk, uint8_t* seg, int64_t bb, int64_t be, uint32_t j_chunk,
+                               const uint64_t* key, hipStream_t s) {
     switch (reduce_by(p)) {
-        case 2: mx_launch_reduce<T, 2, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, s); break;
-        case 4: mx_launch_reduce<T, 4, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, s); break;
-        default: mx_launch_reduce<T, 8, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, s); break;
+        case 2: mx_launch_reduce<T, 2, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, j_chunk, key, s); break;
+        case 4: mx_launch_reduce<T, 4, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, j_chunk, key, s); break;
+        default: mx_launch_reduce<T, 8, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, j_chunk, key, s); break;
     }
 }
 
 template <typename T>
 static int mx_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, int cs, int p, void* tensor, int average,
-                                     uint8_t* out, size_t out_bytes, int target, int bb, int be, hipStream_t s) {
+                                     uint8_t* out, size_t out_bytes, int target, int bb, int be, const uint64_t* key,
+                                     hipStream_t s) {
     using S = typename T::storage;
     if (p <= 0 || cs < 0 || target < 0 || target >= p || !recv || !out) return BAGUA_ERR_INVALID_ARG;
     if (p > kMaxFusedChunks) return BAGUA_ERR_UNSUPPORTED;  // caller runs decompress + reduce + compress
@@ -662,8 +691,9 @@ static int mx_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, int
     S* chunk = tensor ? static_cast<S*>(tensor) + (int64_t)target * cs : nullptr;  // nullptr: not stored
     uint8_t* seg = out + (size_t)target * segb;
     const int blocks = mx_grid(be - bb, kBlock, 1, "BAGUA_TUNE_MX_MIDDLE_BLOCKS");
-    if (mx_hw()) mx_dispatch_reduce<T, true>(blocks, recv, (int64_t)cs, p, average, chunk, seg, bb, be, s);
-    else mx_dispatch_reduce<T, false>(blocks, recv, (int64_t)cs, p, average, chunk, seg, bb, be, s);
+    const uint32_t jc = (uint32_t)((int64_t)target * cs);  // index of the own chunk's first element
+    if (mx_hw()) mx_dispatch_reduce<T, true>(blocks, recv, (int64_t)cs, p, average, chunk, seg, bb, be, jc, key, s);
+    else mx_dispatch_reduce<T, false>(blocks, recv, (int64_t)cs, p, average, chunk, seg, bb, be, jc, key, s);
     return check_launch();
 }
 
@@ -791,17 +821,18 @@ size_t bagua_mxfp4_compressed_bytes(int chunk_size, int num_chunks) {
 
 // the whole-chunk entries are the range [0, nb) (kMxWhole) of the range entries' code
 static int mx_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
-                       uint8_t* output, size_t output_bytes, int target_chunk, int bb, int be, hipStream_t s) {
+                       uint8_t* output, size_t output_bytes, int target_chunk, int bb, int be, const uint64_t* key,
+                       hipStream_t s) {
     switch (dtype) {
         case BAGUA_DTYPE_F32:
             return mx_compress_impl<F32>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                         target_chunk, bb, be, s);
+                                         target_chunk, bb, be, key, s);
         case BAGUA_DTYPE_F16:
             return mx_compress_impl<F16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                         target_chunk, bb, be, s);
+                                         target_chunk, bb, be, key, s);
         case BAGUA_DTYPE_BF16:
             return mx_compress_impl<BF16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                          target_chunk, bb, be, s);
+                                          target_chunk, bb, be, key, s);
     }
     return BAGUA_ERR_UNSUPPORTED;
 }
@@ -821,17 +852,17 @@ static int mx_decompress(int dtype, const uint8_t* input, size_t input_bytes, in
 
 static int mx_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
                                 void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
-                                int bb, int be, hipStream_t s) {
+                                int bb, int be, const uint64_t* key, hipStream_t s) {
     switch (dtype) {
         case BAGUA_DTYPE_F32:
             return mx_reduce_requantize_impl<F32>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
-                                                  output_bytes, target_chunk, bb, be, s);
+                                                  output_bytes, target_chunk, bb, be, key, s);
         case BAGUA_DTYPE_F16:
             return mx_reduce_requantize_impl<F16>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
-                                                  output_bytes, target_chunk, bb, be, s);
+                                                  output_bytes, target_chunk, bb, be, key, s);
         case BAGUA_DTYPE_BF16:
             return mx_reduce_requantize_impl<BF16>(input, input_bytes, chunk_size, num_chunks, tensor, average,
-                                                   output, output_bytes, target_chunk, bb, be, s);
+                                                   output, output_bytes, target_chunk, bb, be, key, s);
     }
     return BAGUA_ERR_UNSUPPORTED;
 }
@@ -839,7 +870,7 @@ static int mx_reduce_requantize(int dtype, const uint8_t* input, size_t input_by
 int bagua_mxfp4_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
                          uint8_t* output, size_t output_bytes, int target_chunk, bagua_stream_t stream) {
     return mx_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, target_chunk,
-                       kMxWhole, kMxWhole, static_cast<hipStream_t>(stream));
+                       kMxWhole, kMxWhole, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int bagua_mxfp4_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
@@ -852,7 +883,8 @@ int bagua_mxfp4_reduce_requantize(int dtype, const uint8_t* input, size_t input_
                                   void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
                                   bagua_stream_t stream) {
     return mx_reduce_requantize(dtype, input, input_bytes, chunk_size, num_chunks, tensor, average, output,
-                                output_bytes, target_chunk, kMxWhole, kMxWhole, static_cast<hipStream_t>(stream));
+                                output_bytes, target_chunk, kMxWhole, kMxWhole, nullptr,
+                                static_cast<hipStream_t>(stream));
 }
 
 // ---- pieces (MXFP4.md, "Pipelined op") ----
@@ -894,7 +926,7 @@ int bagua_mxfp4_compress_range(int dtype, const void* input, int input_num_eleme
                                bagua_stream_t stream) {
     if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
     return mx_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, -1,
-                       block_begin, block_end, static_cast<hipStream_t>(stream));
+                       block_begin, block_end, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int bagua_mxfp4_decompress_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
@@ -909,7 +941,50 @@ int bagua_mxfp4_reduce_requantize_range(int dtype, const uint8_t* input, size_t 
                                         int target_chunk, int block_begin, int block_end, bagua_stream_t stream) {
     if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
     return mx_reduce_requantize(dtype, input, input_bytes, chunk_size, num_chunks, nullptr, average, output,
-                                output_bytes, target_chunk, block_begin, block_end, static_cast<hipStream_t>(stream));
+                                output_bytes, target_chunk, block_begin, block_end, nullptr,
+                                static_cast<hipStream_t>(stream));
+}
+
+// ---- stochastic rounding (MXFP4.md, "Stochastic rounding") ----
+uint64_t bagua_mxfp4_sr_key(uint64_t seed, uint64_t step, int rank, int stage) {
+    return mx_sr_key(seed, step, (uint32_t)rank, (uint32_t)stage);
+}
+
+uint32_t bagua_mxfp4_sr_word(uint64_t key, uint32_t pair_index) {
+    return mx_sr_word((uint32_t)key, (uint32_t)(key >> 32), pair_index);
+}
+
+int bagua_mxfp4_compress_sr(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                            uint8_t* output, size_t output_bytes, int target_chunk, uint64_t key,
+                            bagua_stream_t stream) {
+    return mx_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, target_chunk,
+                       kMxWhole, kMxWhole, &key, static_cast<hipStream_t>(stream));
+}
+
+int bagua_mxfp4_compress_sr_range(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                                  uint8_t* output, size_t output_bytes, int block_begin, int block_end, uint64_t key,
+                                  bagua_stream_t stream) {
+    if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
+    return mx_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, -1,
+                       block_begin, block_end, &key, static_cast<hipStream_t>(stream));
+}
+
+int bagua_mxfp4_reduce_requantize_sr(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                     int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                     int target_chunk, uint64_t key, bagua_stream_t stream) {
+    return mx_reduce_requantize(dtype, input, input_bytes, chunk_size, num_chunks, nullptr, average, output,
+                                output_bytes, target_chunk, kMxWhole, kMxWhole, &key,
+                                static_cast<hipStream_t>(stream));
+}
+
+int bagua_mxfp4_reduce_requantize_sr_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                           int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                           int target_chunk, int block_begin, int block_end, uint64_t key,
+                                           bagua_stream_t stream) {
+    if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
+    return mx_reduce_requantize(dtype, input, input_bytes, chunk_size, num_chunks, nullptr, average, output,
+                                output_bytes, target_chunk, block_begin, block_end, &key,
+                                static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

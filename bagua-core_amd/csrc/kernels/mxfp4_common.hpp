@@ -95,6 +95,96 @@ MX_HD void mx_encode_block(const float (&x)[kMxBlock], float maxf, uint32_t& byt
     for (int e = 0; e < kMxBlock; ++e) w[e / 8] |= mx_quant(mx_clamp(x[e], maxf), inv) << (4 * (e % 8));
 }
 
+// ---- stochastic rounding (MXFP4.md, "Stochastic rounding") ---------------------------
+// The plain block encode with one change: an element goes to the grid value above it with
+// probability equal to its fractional position between the two neighbours, decided by 16
+// bits r of a counter-based hash of (key, element index in the tensor).  Scale byte, NaN
+// blocks, clamps and invalid elements are the plain rule's.
+
+// splitmix64's finaliser; the key of one (seed, step, rank, stage) is host-only arithmetic
+inline uint64_t mx_sm64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+inline uint64_t mx_sr_key(uint64_t seed, uint64_t step, uint32_t rank, uint32_t stage) {
+    return mx_sm64(mx_sm64(mx_sm64(seed) ^ step) ^ (2ull * rank + stage));
+}
+
+// the word of element pair `pair` = j >> 1: its low half serves the even j, its high half the odd
+MX_HD uint32_t mx_fmix32(uint32_t h) {
+    h ^= h >> 16;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    h *= 0xc2b2ae35u;
+    return h ^ (h >> 16);
+}
+MX_HD uint32_t mx_sr_word(uint32_t k0, uint32_t k1, uint32_t pair) { return mx_fmix32(pair + k0) ^ k1; }
+
+// r of the N elements j0 .. j0 + N - 1 (N even): N / 2 hashes when j0 is even, one more when
+// a pair straddles each end
+template <int N>
+MX_HD void mx_sr_bits(uint32_t j0, uint32_t k0, uint32_t k1, uint32_t (&r)[N]) {
+    const uint32_t p0 = j0 >> 1;
+    if ((j0 & 1u) == 0u) {
+#pragma unroll
+        for (int h = 0; h < N / 2; ++h) {
+            const uint32_t w = mx_sr_word(k0, k1, p0 + h);
+            r[2 * h] = w & 0xffffu;
+            r[2 * h + 1] = w >> 16;
+        }
+    } else {
+        r[0] = mx_sr_word(k0, k1, p0) >> 16;
+#pragma unroll
+        for (int h = 1; h < N / 2; ++h) {
+            const uint32_t w = mx_sr_word(k0, k1, p0 + h);
+            r[2 * h - 1] = w & 0xffffu;
+            r[2 * h] = w >> 16;
+        }
+        r[N - 1] = mx_sr_word(k0, k1, p0 + N / 2) & 0xffffu;
+    }
+}
+
+// mx_quant with the stochastic rule: y = |x * 2^-e| <= 6 lies on the grid of step s = 0.5
+// below 2, 1 below 4, 2 from 4, s = 2^(max(E, 127) - 128).  Q = floor(y / s * 2^16) (the
+// product with 2^16 / s is exact, at most 3 * 2^16, and the conversion truncates) holds
+// n = floor(y / s) above its 16 fraction bits F, so (Q + r) >> 16 = n + ((F + r) >> 16),
+// and the code of (n + up) * s is n + up + 2 * (max(E, 127) - 127) as in mx_quant.
+MX_HD uint32_t mx_quant_sr(float x, float inv, uint32_t r) {
+    const float y = x * inv;
+    const uint32_t yb = mx_bits(y), ya = yb & 0x7fffffffu;
+    const uint32_t me = (ya > 0x3f800000u ? ya : 0x3f800000u) & 0x7f800000u;
+    const uint32_t q = (uint32_t)(mx_float(ya) * mx_float(0x87800000u - me));
+    return (((q + r) >> 16) + (me >> 22) - 254u) | ((yb >> 28) & 8u);
+}
+
+// mx_encode_block under the stochastic rule; j0: the index of x[0] in the whole tensor
+MX_HD void mx_encode_block_sr(const float (&x)[kMxBlock], float maxf, uint32_t j0, uint32_t k0, uint32_t k1,
+                              uint32_t& byte, uint32_t (&w)[4]) {
+    uint32_t am = 0;
+#pragma unroll
+    for (int e = 0; e < kMxBlock; ++e) {
+        const uint32_t a = mx_bits(x[e]) & 0x7fffffffu;
+        am = a > am ? a : am;
+    }
+    w[0] = w[1] = w[2] = w[3] = 0u;
+    if (am > 0x7f800000u) {  // a NaN in the block
+        byte = kMxNanScale;
+        return;
+    }
+    const uint32_t mb = mx_bits(maxf);
+    byte = mx_scale_byte(am < mb ? am : mb);
+    const float inv = mx_inv_scale(byte);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t r[8];
+        mx_sr_bits<8>(j0 + 8u * k, k0, k1, r);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) w[k] |= mx_quant_sr(mx_clamp(x[8 * k + e], maxf), inv, r[e]) << (4 * e);
+    }
+}
+
 // ---- error feedback (MXFP4.md, "Error feedback") -----------------------------------
 // K: 0 f32, 1 f16, 2 bf16 (the BAGUA_DTYPE_* codes).
 

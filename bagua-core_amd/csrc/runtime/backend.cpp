@@ -69,6 +69,13 @@ struct BaguaBucketC {
     int sched_index = 0;  // position in the scheduler's registration order (its lane)
     std::vector<BucketTensor> tensors;
     std::vector<bagua_bucket_op_t> ops;
+    // op i's executions so far (guarded by `mu`): the step of a stochastic-rounding op's keys,
+    // 0 at the first execution after the op was appended
+    std::vector<uint64_t> op_steps;
+    uint64_t next_step(size_t i) {
+        std::lock_guard<std::mutex> g(mu);
+        return i < op_steps.size() ? op_steps[i]++ : 0;
+    }
     // readiness per tensor (guarded by `mu`): a mark is one hash lookup and a flag, and
     // the readiness test a compare -- the reference's name set (datatypes/mod.rs:1256-1266)
     // costs a walk over the bucket per mark
@@ -129,8 +136,8 @@ bool ops_async(const std::vector<bagua_bucket_op_t>& ops) {
     return false;
 }
 
-int run_op(const bagua_bucket_op_t& op, const bagua_tensor_t* flat, const char* bucket_name, hipStream_t s,
-           bool async) {
+int run_op(BaguaBucketC* b, size_t index, const bagua_bucket_op_t& op, const bagua_tensor_t* flat,
+           const char* bucket_name, hipStream_t s, bool async) {
     if (op.intranode) {  // hierarchical mode (communicators/mod.rs:390-427)
         switch (op.kind) {
             case BAGUA_BUCKET_OP_CENTRALIZED_LOW_PRECISION:
@@ -164,6 +171,8 @@ int run_op(const bagua_bucket_op_t& op, const bagua_tensor_t* flat, const char* 
         case BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK:
             return bagua_centralized_mxfp4_error_feedback(op.comm, flat, op.average, &op.ef_worker_carry,
                                                           &op.ef_server_carry);
+        case BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC:
+            return bagua_centralized_mxfp4_stochastic(op.comm, flat, op.average, op.sr_seed, b->next_step(index), 0);
         case BAGUA_BUCKET_OP_CALLBACK:
             // the callback sees the previous ops' results, as in the reference (their
             // Drop synced), also when the worker runs the ops async
@@ -244,8 +253,8 @@ int execute_bucket(BaguaBucketC* b, const std::vector<BucketTensor>& tensors, co
     if (contig) {
         if ((rc = order_after(os, s)) != BAGUA_OK) return rc;
         const bagua_tensor_t flat{first.ptr, total_alloc, total_alloc, first.dtype, first.device_id};
-        for (const bagua_bucket_op_t& op : ops)
-            if ((rc = run_op(op, &flat, b->name.c_str(), os, async)) != BAGUA_OK) break;
+        for (size_t i = 0; i < ops.size(); ++i)
+            if ((rc = run_op(b, i, ops[i], &flat, b->name.c_str(), os, async)) != BAGUA_OK) break;
         const int rc2 = order_after(s, os);  // the caller's stream sees the results
         return rc != BAGUA_OK ? rc : rc2;
     }
@@ -262,8 +271,8 @@ int execute_bucket(BaguaBucketC* b, const std::vector<BucketTensor>& tensors, co
     }
     if ((rc = order_after(os, s)) != BAGUA_OK) return rc;  // the ops read the packed buffer
     const bagua_tensor_t flat{buf.ptr(), total, total_alloc, first.dtype, first.device_id};
-    for (const bagua_bucket_op_t& op : ops)
-        if ((rc = run_op(op, &flat, b->name.c_str(), os, async)) != BAGUA_OK) break;
+    for (size_t i = 0; i < ops.size(); ++i)
+        if ((rc = run_op(b, i, ops[i], &flat, b->name.c_str(), os, async)) != BAGUA_OK) break;
     // :1043-1070 copy back, then wait for the stream (the buffer returns to the pool);
     // async: the buffer returns to the pool behind the stream instead.  Queued work
     // of a failed op still writes the buffer: the copy-back is skipped, the buffer's
@@ -627,8 +636,20 @@ int bagua_bucket_append_op(BaguaBucketC* b, const bagua_bucket_op_t* op) {
     if (op->kind != BAGUA_BUCKET_OP_CALLBACK && !op->comm && !op->intranode) return BAGUA_ERR_INVALID_ARG;
     if (op->intranode && op->intranode->rank == 0 && !op->comm) return BAGUA_ERR_INVALID_ARG;
     if (op->kind < BAGUA_BUCKET_OP_CENTRALIZED_LOW_PRECISION ||
-        op->kind > BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK)
+        op->kind > BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC)
         return BAGUA_ERR_UNSUPPORTED;
+    // sr_seed was appended for the stochastic op: the older kinds are read up to it only, so
+    // callers built against the shorter struct stay valid for them
+    bagua_bucket_op_t copy{};
+    std::memcpy(&copy, op,
+                op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC ? sizeof(copy)
+                                                                         : offsetof(bagua_bucket_op_t, sr_seed));
+    if (op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC) {
+        // MXFP4 codec only, no hierarchical mode, no error-feedback state beside it
+        if (op->intranode || op->compression != BAGUA_COMPRESSION_MXFP4) return BAGUA_ERR_UNSUPPORTED;
+        if (op->ef_worker_carry.ptr || op->ef_worker_scales.ptr || op->ef_server_carry.ptr || op->ef_server_scale.ptr)
+            return BAGUA_ERR_INVALID_ARG;
+    }
     if (op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK) {
         // MXFP4 codec only, no hierarchical mode, both residuals present, no scale tensors
         if (op->intranode || op->compression != BAGUA_COMPRESSION_MXFP4) return BAGUA_ERR_UNSUPPORTED;
@@ -644,7 +665,8 @@ int bagua_bucket_append_op(BaguaBucketC* b, const bagua_bucket_op_t* op) {
             return BAGUA_ERR_INVALID_ARG;
     }
     std::lock_guard<std::mutex> g(b->mu);
-    b->ops.push_back(*op);
+    b->ops.push_back(copy);
+    b->op_steps.push_back(0);
     return BAGUA_OK;
 }
 
@@ -652,6 +674,7 @@ int bagua_bucket_clear_ops(BaguaBucketC* b) {
     if (!b) return BAGUA_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(b->mu);
     b->ops.clear();
+    b->op_steps.clear();
     return BAGUA_OK;
 }
 

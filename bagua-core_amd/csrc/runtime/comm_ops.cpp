@@ -148,7 +148,8 @@ int env_int(const char* name, long dflt);
 int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_tensor_t* t, uint64_t chunk,
                    int sched, int average);
 enum { kOpCentralized = 1, kOpCentralizedUnfused, kOpCentralizedPipelined, kOpOneBitPipelined, kOpRing,
-       kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback, kOpMxfp4Pipelined };
+       kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback, kOpMxfp4Pipelined, kOpMxfp4Stochastic,
+       kOpMxfp4StochasticPipelined };
 
 // The alltoall of the unpieced ops: slot j of recv <- rank j's segment `rank`.  One rank
 // receives its own bytes by a device copy (RCCL's single-rank copy kernel was slower: 1 GiB
@@ -174,7 +175,24 @@ int composed_ef_middle(const bagua_tensor_t* t, int method, const Chunking& k, i
                        sb + (size_t)k.rank * co, co);
 }
 
-int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int method, bool fused) {
+// The keys of one execution of the MXFP4 op with stochastic rounding (MXFP4.md): stage 0,
+// this rank's encode of every chunk, and stage 1, its re-encode of the reduced own chunk.
+struct MxSrKeys {
+    uint64_t worker, server;
+};
+
+// bagua_tensor_compress_into for the MXFP4 codec under a key; cs fits an int (plan, below)
+int mxfp4_compress_keyed(const bagua_tensor_t* t, const Chunking& k, int target, uint64_t key, const bagua_tensor_t& out,
+                         uint64_t stream) {
+    if (k.cs > 0x7fffffffULL || t->num_elem > 0x7fffffffULL) return BAGUA_ERR_INVALID_ARG;
+    return bagua_mxfp4_compress_sr(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)k.cs, k.p,
+                                   (uint8_t*)(uintptr_t)out.ptr, k.S, target, key, (void*)(uintptr_t)stream);
+}
+
+// sr (MXFP4 only): both encodes round stochastically under its keys; every other step,
+// buffer and collective is the plain op's
+int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int method, bool fused,
+                const MxSrKeys* sr = nullptr) {
     OpTimer tm;
     double ph[5] = {0, 0, 0, 0, 0};
     struct Commit {
@@ -191,7 +209,8 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
     int rc = plan(c, t, method, &k);
     if (rc) return rc;
     DeviceGuard guard(c->device_id);
-    if ((rc = check_schedule(c, fused ? kOpCentralized : kOpCentralizedUnfused, method, t, k.cs, 1, average)))
+    if ((rc = check_schedule(c, sr ? kOpMxfp4Stochastic : fused ? kOpCentralized : kOpCentralizedUnfused, method, t,
+                             k.cs, 1, average)))
         return rc;
     const uint64_t s = (uint64_t)(uintptr_t)c->stream;
     if (k.p == 1 && fused && method == BAGUA_COMPRESSION_MINMAX_UINT8 && t->num_elem == t->num_elem_allocated &&
@@ -233,7 +252,8 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
     const bagua_tensor_t rv = u8_view(recv.ptr(), k.S, c->device_id);
     ph[0] = tm.lap();
     // 1. compress every chunk (target -1)
-    TRY(bagua_tensor_compress_into(t, method, k.p, s, -1, &sv));
+    if (sr) TRY(mxfp4_compress_keyed(t, k, -1, sr->worker, sv, s));
+    else TRY(bagua_tensor_compress_into(t, method, k.p, s, -1, &sv));
     ph[1] = tm.lap();
     if (!self_alias) TRY(alltoall_or_copy(c, k, send.as<void>(), recv.as<void>()));
     uint8_t* const rbuf = self_alias ? send.as<uint8_t>() : recv.as<uint8_t>();
@@ -285,15 +305,18 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
         else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
     } else if (fused && method == BAGUA_COMPRESSION_MXFP4 && t->num_elem == t->num_elem_allocated) {
         // one kernel, no workspace; the reduced chunk is not stored (step 5 rewrites every element)
-        rc = bagua_mxfp4_reduce_requantize(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, nullptr, average,
-                                           send.as<uint8_t>(), k.S, k.rank, (void*)(uintptr_t)s);
+        rc = sr ? bagua_mxfp4_reduce_requantize_sr(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, average,
+                                                   send.as<uint8_t>(), k.S, k.rank, sr->server, (void*)(uintptr_t)s)
+                : bagua_mxfp4_reduce_requantize(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, nullptr, average,
+                                                send.as<uint8_t>(), k.S, k.rank, (void*)(uintptr_t)s);
         if (rc == BAGUA_OK) done = true;
         else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
     }
     if (!done) {
         TRY(bagua_tensor_decompress_from(t, method, k.p, rview, s));
         TRY(bagua_tensor_reduce_inplace(t, k.p, k.rank, average, s));
-        TRY(bagua_tensor_compress_into(t, method, k.p, s, k.rank, &sv));
+        if (sr) TRY(mxfp4_compress_keyed(t, k, k.rank, sr->server, sv, s));
+        else TRY(bagua_tensor_compress_into(t, method, k.p, s, k.rank, &sv));
     }
     // 4. allgather the requantised chunks in place (one rank: nothing to move), 5. decompress everything
     if (k.p > 1) TRY(bagua_comm_allgather_inplace(c, &sv));
@@ -757,7 +780,12 @@ int centralized_onebit_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
 //   (E encode piece q of all chunks, A its alltoall, M the fused middle step on piece q of
 //    the own chunk, G its allgather, D decode piece q of all chunks; M_q waits for A_q
 //    only, G_q for M_q, D_q for G_q; the side stream posts A0 .. Ak, then G0 .. Gk)
-int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int pieces) {
+//
+// sr: the same schedule with both encodes stochastic (MXFP4.md, "Stochastic rounding").  A
+// word depends on the key and the element's index alone, so every piece count gives the
+// unpieced op's bytes.
+int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int pieces,
+                                const MxSrKeys* sr = nullptr) {
     Chunking k;
     if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
     int rc = plan(c, t, BAGUA_COMPRESSION_MXFP4, &k);
@@ -768,14 +796,17 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
     // unpieced: one rank (no exchange to hide) and the shapes the fused middle step or the
     // vector paths cannot take -- decided from values equal on every rank only
     // (vec = 1: a segment is whole 32-B lines, only the chunk has to be whole 16-B vectors)
-    if (pieces == 1 || k.p == 1 || !pipeline_fits(t, k, 1)) return centralized(c, t, average, BAGUA_COMPRESSION_MXFP4, true);
+    if (pieces == 1 || k.p == 1 || !pipeline_fits(t, k, 1))
+        return centralized(c, t, average, BAGUA_COMPRESSION_MXFP4, true, sr);
     if (t->ptr % 16)  // this rank alone: the same schedule on an aligned staging copy
         return with_aligned_copy(c, {t}, [&](const std::vector<const bagua_tensor_t*>& u) {
-            return centralized_pipelined_mxfp4(c, u[0], average, caller);
+            return centralized_pipelined_mxfp4(c, u[0], average, caller, sr);
         });
     const int sched = op_schedule(c->cfg, pieces, caller);
     DeviceGuard guard(c->device_id);
-    if ((rc = check_schedule(c, kOpMxfp4Pipelined, BAGUA_COMPRESSION_MXFP4, t, k.cs, sched, average))) return rc;
+    if ((rc = check_schedule(c, sr ? kOpMxfp4StochasticPipelined : kOpMxfp4Pipelined, BAGUA_COMPRESSION_MXFP4, t, k.cs,
+                             sched, average)))
+        return rc;
     if (c->ensure_side(4 * (size_t)pieces + 1)) return finish(c, BAGUA_ERR_HIP);
     hipStream_t s0 = c->stream;
     hipEvent_t* encoded = c->events.data();
@@ -796,7 +827,9 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
     // events are recorded all the same)
     for (int q = 0; q < pieces; ++q) {
         if (tab[q].b < tab[q].e)
-            TRY2(bagua_mxfp4_compress_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, tab[q].b, tab[q].e, s0));
+            TRY2(sr ? bagua_mxfp4_compress_sr_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, tab[q].b, tab[q].e,
+                                                    sr->worker, s0)
+                    : bagua_mxfp4_compress_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, tab[q].b, tab[q].e, s0));
         HIP2(hipEventRecord(encoded[q], s0));
     }
     TRY2(exchange_pieces(c, k, sb, rb, tab, true, encoded, exchanged));
@@ -805,8 +838,10 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
     for (int q = 0; q < pieces; ++q) {
         HIP2(hipStreamWaitEvent(s0, exchanged[q], 0));
         if (tab[q].b < tab[q].e)
-            TRY2(bagua_mxfp4_reduce_requantize_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, tab[q].b, tab[q].e,
-                                                     s0));
+            TRY2(sr ? bagua_mxfp4_reduce_requantize_sr_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, tab[q].b,
+                                                             tab[q].e, sr->server, s0)
+                    : bagua_mxfp4_reduce_requantize_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, tab[q].b,
+                                                          tab[q].e, s0));
         HIP2(hipEventRecord(requantised[q], s0));
     }
     // 3. allgather + decode piece by piece
@@ -954,6 +989,17 @@ int bagua_centralized_mxfp4_error_feedback(BaguaSingleCommunicatorC* c, const ba
         (rc = ef_tensor(server_residual, t->num_elem / p, t->device_id, &server)))
         return rc;
     return centralized_mxfp4_ef(c, t, average, worker, server);
+}
+
+int bagua_centralized_mxfp4_stochastic(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
+                                       uint64_t seed, uint64_t step, int pieces) {
+    // every refusal before anything is launched or posted
+    if (!c || !c->t || !t || !t->ptr) return BAGUA_ERR_INVALID_ARG;
+    if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
+    if (!is_float_dtype(t->dtype)) return BAGUA_ERR_UNSUPPORTED;
+    // the keys are this rank's alone: no byte count and no collective depends on them
+    const MxSrKeys sr{bagua_mxfp4_sr_key(seed, step, (int)c->rank, 0), bagua_mxfp4_sr_key(seed, step, (int)c->rank, 1)};
+    return centralized_pipelined_mxfp4(c, t, average, pieces, &sr);
 }
 
 int bagua_centralized_low_precision_synchronous(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,

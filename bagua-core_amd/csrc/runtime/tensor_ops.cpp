@@ -239,6 +239,33 @@ int bagua_tensor_compress_error_feedback(const bagua_tensor_t* t, int n_chunks, 
     return BAGUA_OK;
 }
 
+// the MXFP4 compress with stochastic rounding (bagua_mxfp4_compress_sr), rank 0 and stage 0
+int bagua_tensor_compress_mxfp4_stochastic(const bagua_tensor_t* t, int n_chunks, uint64_t stream, uint64_t seed,
+                                           uint64_t step, bagua_tensor_t* out) {
+    size_t cs = 0;
+    int rc = check_chunks(t, n_chunks, &cs);
+    if (rc) return rc;
+    if (!out) return BAGUA_ERR_INVALID_ARG;
+    if (!codec_dtype(t->dtype)) return BAGUA_ERR_UNSUPPORTED;
+    const size_t bytes = bagua_mxfp4_compressed_bytes((int)cs, n_chunks);
+    if (!bytes) return BAGUA_ERR_UNSUPPORTED;
+    uint64_t p = 0;
+    if ((rc = pool_alloc(t->device_id, bytes, &p)) != BAGUA_OK) return rc;
+    rc = bagua_mxfp4_compress_sr(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)cs, n_chunks,
+                                 (uint8_t*)(uintptr_t)p, bytes, -1, bagua_mxfp4_sr_key(seed, step, 0, 0),
+                                 (void*)(uintptr_t)stream);
+    if (rc) {
+        pool_free(p);
+        return rc;
+    }
+    out->ptr = p;
+    out->num_elem = bytes;
+    out->num_elem_allocated = bytes;
+    out->dtype = BAGUA_DTYPE_U8;
+    out->device_id = t->device_id;
+    return BAGUA_OK;
+}
+
 // the MXFP4 compress with error-feedback state (bagua_mxfp4_compress_ef): `residual`
 // (num_elem F32) on the tensor's device, 16-B aligned
 int bagua_tensor_compress_mxfp4_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,

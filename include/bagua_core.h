@@ -102,6 +102,10 @@ int bagua_tensor_compress_error_feedback(const bagua_tensor_t* t, int n_chunks, 
  * aligned, updated in place on `stream`; every chunk compressed. */
 int bagua_tensor_compress_mxfp4_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
                                                const bagua_tensor_t* residual, bagua_tensor_t* out);
+/* bagua_tensor_compress with "MXFP4" and stochastic rounding under the key
+ * bagua_mxfp4_sr_key(seed, step, 0, 0); bagua_tensor_decompress_from decodes it. */
+int bagua_tensor_compress_mxfp4_stochastic(const bagua_tensor_t* t, int n_chunks, uint64_t stream, uint64_t seed,
+                                           uint64_t step, bagua_tensor_t* out);
 /* RawBaguaTensor::decompress_from (datatypes/mod.rs:398-446) */
 int bagua_tensor_decompress_from(const bagua_tensor_t* t, int method, int n_chunks,
                                  const bagua_tensor_t* compressed, uint64_t stream);
@@ -175,6 +179,16 @@ BaguaSingleCommunicatorC* bagua_loopback_communicator_create(void* group, size_t
 int bagua_comm_set_async(BaguaSingleCommunicatorC* comm, int on);
 /* CentralizedLowPrecisionSynchronous::execute_background_communication on one
  * flat communication tensor (centralized_low_precision_synchronous.rs:16-73). */
+/* The MXFP4 op with stochastic rounding (MXFP4.md, "Stochastic rounding"): the plain op's
+ * paths, buffers and collectives (pipelined over `pieces` as
+ * bagua_centralized_low_precision_pipelined with BAGUA_COMPRESSION_MXFP4; unpieced for one
+ * rank, one piece and the shapes the pipeline refuses; composed middle step for partly
+ * valid tensors and more than 16 ranks), both encodes rounding stochastically under the
+ * keys bagua_mxfp4_sr_key(seed, step, this rank, 0 / 1).  No state.  Every piece count
+ * gives the same bytes.  Seeds and steps need not agree across ranks.  There is no
+ * hierarchical form. */
+int bagua_centralized_mxfp4_stochastic(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t, int average,
+                                       uint64_t seed, uint64_t step, int pieces);
 int bagua_centralized_low_precision_synchronous(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t,
                                                 int average, int method);
 /* The same op with each chunk cut into `pieces` element ranges, the exchange of
@@ -309,7 +323,8 @@ enum {
     BAGUA_BUCKET_OP_DECENTRALIZED_LOW_PRECISION = 3, /* decentralized_low_precision_synchronous.rs */
     BAGUA_BUCKET_OP_CALLBACK = 4,                    /* python_ffi_op.rs: callback(user, bucket name) */
     BAGUA_BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK = 5, /* bagua_centralized_onebit_error_feedback */
-    BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK = 6   /* bagua_centralized_mxfp4_error_feedback */
+    BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK = 6,  /* bagua_centralized_mxfp4_error_feedback */
+    BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC = 7       /* bagua_centralized_mxfp4_stochastic */
 };
 
 typedef struct bagua_bucket_op {
@@ -330,6 +345,12 @@ typedef struct bagua_bucket_op {
      * BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK: its two residuals travel in
      * ef_worker_carry and ef_server_carry; the two scale fields must be absent. */
     bagua_tensor_t ef_worker_carry, ef_worker_scales, ef_server_carry, ef_server_scale;
+    /* BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC: the seed of the op's rounding (compression
+     * must be BAGUA_COMPRESSION_MXFP4, intranode and the four state tensors absent).  The
+     * bucket counts the op's executions: the first after the append runs step 0, the next step
+     * 1, ...; an execution replayed from a captured graph repeats the step it was captured with.
+     * Appended last: bagua_bucket_append_op reads the other kinds up to this field only. */
+    uint64_t sr_seed;
 } bagua_bucket_op_t;
 
 /* NULL on error (*status says why): empty list, mixed dtype / device, allocated < num_elem */

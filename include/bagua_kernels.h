@@ -293,6 +293,38 @@ int bagua_mxfp4_reduce_requantize_ef(int dtype, const uint8_t* input, size_t inp
                                      int num_chunks, int average, uint8_t* output, size_t output_bytes,
                                      int target_chunk, float* residual, bagua_stream_t stream);
 
+/* MXFP4 with stochastic rounding (MXFP4.md, "Stochastic rounding"): the plain encode except
+ * that an element between two grid values goes to the upper one with probability equal to
+ * its fractional position, so the decode's expectation is the input.  No state; wire format,
+ * scale bytes, sizes and the decode are the plain codec's.  The choice is made by 16 bits of
+ * a counter-based hash of `key` and the element's index in the whole tensor (chunk *
+ * chunk_size + index in chunk, as uint32), so the bytes depend on neither chunking, range nor
+ * grid.
+ *   bagua_mxfp4_sr_key: host arithmetic, no GPU -- the key of one (seed, step, rank, stage);
+ *     stage 0 is the worker encode, stage 1 the re-encode of the reduced own chunk.  Ranks
+ *     need different keys for their rounding errors to average out.
+ *   bagua_mxfp4_sr_word: host arithmetic -- the 32-bit word of element pair `pair_index` =
+ *     j >> 1; element j takes its low 16 bits when j is even, its high 16 bits when odd.
+ *   bagua_mxfp4_compress_sr / _range: bagua_mxfp4_compress / _range with the key.
+ *   bagua_mxfp4_reduce_requantize_sr / _range: the middle step, never storing the reduced
+ *     chunk; byte for byte decompress + bagua_reduce_chunks + compress_sr(target_chunk).
+ * Refusals are the plain entries', BAGUA_ERR_UNSUPPORTED past 16 segments included. */
+uint64_t bagua_mxfp4_sr_key(uint64_t seed, uint64_t step, int rank, int stage);
+uint32_t bagua_mxfp4_sr_word(uint64_t key, uint32_t pair_index);
+int bagua_mxfp4_compress_sr(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                            uint8_t* output, size_t output_bytes, int target_chunk, uint64_t key,
+                            bagua_stream_t stream);
+int bagua_mxfp4_compress_sr_range(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                                  uint8_t* output, size_t output_bytes, int block_begin, int block_end, uint64_t key,
+                                  bagua_stream_t stream);
+int bagua_mxfp4_reduce_requantize_sr(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                     int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                     int target_chunk, uint64_t key, bagua_stream_t stream);
+int bagua_mxfp4_reduce_requantize_sr_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                           int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                           int target_chunk, int block_begin, int block_end, uint64_t key,
+                                           bagua_stream_t stream);
+
 /* The decentralized ring op (decentralized_low_precision_synchronous.rs:45-64,126-151) with the
  * MXFP4 codec, fused (MXFP4.md, "Ring op").  The segment is the num_chunks = 1 layout,
  * bagua_mxfp4_compressed_bytes(num_elem, 1) bytes.  Byte for byte what the elementwise

@@ -7,9 +7,15 @@
 //                                                              bytes and the 32 new residuals out, per block)
 //   mxfp4_host_check ring MAXF_BITS DTYPE N < tensors > out  (t, w, l, r of N elements of T in; the four tensors
 //                                                              after one rank's ring op, then the segment, out)
+//   mxfp4_host_check sr MAXF_BITS KEY J0 < blocks.f32 > bytes  (stochastic rounding under the 64-bit key KEY, hex:
+//                                                              consecutive blocks, the first element of the first
+//                                                              block having index J0 in its tensor; output as encode)
+//   mxfp4_host_check srr MAXF_BITS < blocks > bytes            (32 f32, then the 32 elements' r as u32, in; output as
+//                                                              encode: mx_quant_sr under explicit r values)
 // MAXF_BITS: the f32 bits of the largest finite T, in hex; DTYPE: 0 f32, 1 f16, 2 bf16.
 // tests/test_mxfp4_cpu.py compares both directions with the numpy reference,
-// tests/test_mxfp4_ef_cpu.py the error-feedback rule, tests/test_mxfp4_ring_cpu.py the ring op.
+// tests/test_mxfp4_ef_cpu.py the error-feedback rule, tests/test_mxfp4_ring_cpu.py the ring op,
+// tests/test_mxfp4_sr_cpu.py stochastic rounding.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -98,6 +104,38 @@ int main(int argc, char** argv) {
             case 2: return run_ef<2>(m);
         }
         return 2;
+    }
+    if (argc == 5 && !strcmp(argv[1], "sr")) {
+        const float m = mx_float((uint32_t)strtoul(argv[2], nullptr, 16));
+        const uint64_t key = strtoull(argv[3], nullptr, 16);
+        uint32_t j = (uint32_t)strtoull(argv[4], nullptr, 10);
+        float x[kMxBlock];
+        for (; fread(x, sizeof(float), kMxBlock, stdin) == (size_t)kMxBlock; j += kMxBlock) {
+            uint32_t byte, w[4];
+            mx_encode_block_sr(x, m, j, (uint32_t)key, (uint32_t)(key >> 32), byte, w);
+            const uint8_t b = (uint8_t)byte;
+            fwrite(&b, 1, 1, stdout);
+            fwrite(w, 4, 4, stdout);
+        }
+        return 0;
+    }
+    if (argc == 3 && !strcmp(argv[1], "srr")) {
+        const float m = mx_float((uint32_t)strtoul(argv[2], nullptr, 16));
+        struct { float x[kMxBlock]; uint32_t r[kMxBlock]; } in;
+        while (fread(&in, sizeof(in), 1, stdin) == 1) {
+            uint32_t byte, w[4];
+            mx_encode_block(in.x, m, byte, w);  // the scale byte is the plain encode's
+            if (byte != kMxNanScale) {
+                const float inv = mx_inv_scale(byte);
+                w[0] = w[1] = w[2] = w[3] = 0u;
+                for (int e = 0; e < kMxBlock; ++e)
+                    w[e / 8] |= mx_quant_sr(mx_clamp(in.x[e], m), inv, in.r[e] & 0xffffu) << (4 * (e % 8));
+            }
+            const uint8_t b = (uint8_t)byte;
+            fwrite(&b, 1, 1, stdout);
+            fwrite(w, 4, 4, stdout);
+        }
+        return 0;
     }
     if (argc != 3) return 2;
     const float maxf = mx_float((uint32_t)strtoul(argv[2], nullptr, 16));
