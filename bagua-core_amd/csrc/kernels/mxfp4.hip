@@ -19,6 +19,12 @@
 // HW = true takes gfx950's conversions (v_cvt_scalef32_pk_fp4_f32 / _pk_f32_fp4) for the
 // rounding to and from E2M1; the scale byte, NaN blocks, the inf and largest-finite
 // clamps and the rounding to T stay in the arithmetic of mxfp4_common.hpp.
+//
+// The kernels here are compositions of the steps in mxfp4_device.hpp, which mxfp4_ring.hip
+// shares: the tile load of one tensor, the lane's part of a cooperative block encode, the
+// store of a block's result with the slack rule, the decode-and-tree-sum of one block of the
+// received segments, the residual of a block.  What is left in this file is each kernel's
+// geometry, its order of steps, the error-feedback residual rule and the launchers.
 #include <algorithm>
 #include <cstdint>
 
@@ -55,14 +61,8 @@ __device__ __forceinline__ void mx_encode(const float (&x)[kMxBlock], float maxf
             return;
         }
         byte = mx_scale_byte(min(am, __float_as_uint(maxf)));
-        const float scale = __uint_as_float(byte << 23);  // the conversion reads its exponent: 2^(byte - 127)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            w[k] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w[k], mx_clamp(x[8 * k], maxf), mx_clamp(x[8 * k + 1], maxf), scale, 0);
-            w[k] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w[k], mx_clamp(x[8 * k + 2], maxf), mx_clamp(x[8 * k + 3], maxf), scale, 1);
-            w[k] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w[k], mx_clamp(x[8 * k + 4], maxf), mx_clamp(x[8 * k + 5], maxf), scale, 2);
-            w[k] = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w[k], mx_clamp(x[8 * k + 6], maxf), mx_clamp(x[8 * k + 7], maxf), scale, 3);
-        }
+        for (int k = 0; k < 4; ++k) w[k] = mx_quant_lane<8, kMxHw>(x + 8 * k, byte, maxf);
     }
 }
 
@@ -112,67 +112,16 @@ __global__ __launch_bounds__(kBlock) void mxfp4_encode_kernel(const typename T::
     for (int64_t t = wave; t < tiles; t += nwaves) {
         const int64_t b0 = t * TB;
         float f[R][N];
-        if (vec && (b0 + TB) * kMxBlock <= n) {
-            uint4 raw[R];
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const S* p = src + (b0 + k * BW) * kMxBlock + lane * N;
-                raw[k] = nt_load16(p);
-            }
-#pragma unroll
-            for (int k = 0; k < R; ++k) unpack16<T>(raw[k], f[k]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < R; ++k)
-#pragma unroll
-                for (int e = 0; e < N; ++e) {
-                    const int64_t j = (b0 + k * BW) * kMxBlock + lane * N + e;
-                    f[k][e] = j < n ? T::to_f(src[j]) : 0.0f;
-                }
-        }
+        mx_load_tile<T, true>(src, b0, lane, n, vec && (b0 + TB) * kMxBlock <= n, f);
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            uint32_t am = 0;
-#pragma unroll
-            for (int e = 0; e < N; ++e) am = max(am, __float_as_uint(f[k][e]) & 0x7fffffffu);
-#pragma unroll
-            for (int o = 1; o < G; o <<= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, kWave));
+            const uint32_t am = mx_block_amax<N>(f[k]);
             const int64_t b = b0 + k * BW + lb;
             if (b >= nb) continue;
-            uint32_t byte = kMxNanScale, w = 0;
-            if (am <= 0x7f800000u) {
-                byte = mx_scale_byte(min(am, __float_as_uint(maxf)));
-                if constexpr (SR) {
-                    const float inv = mx_inv_scale(byte);
-                    uint32_t r[N];
-                    mx_sr_bits<N>((uint32_t)((int64_t)c * cs + (bb + b0 + k * BW) * kMxBlock + lane * N), k0, k1, r);
-#pragma unroll
-                    for (int e = 0; e < N; ++e) w |= mx_quant_sr(mx_clamp(f[k][e], maxf), inv, r[e]) << (4 * e);
-                } else if constexpr (HW) {
-                    const float scale = __uint_as_float(byte << 23);
-                    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(f[k][0], maxf), mx_clamp(f[k][1], maxf), scale, 0);
-                    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(f[k][2], maxf), mx_clamp(f[k][3], maxf), scale, 1);
-                    if constexpr (N == 8) {
-                        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(f[k][4], maxf), mx_clamp(f[k][5], maxf), scale, 2);
-                        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(f[k][6], maxf), mx_clamp(f[k][7], maxf), scale, 3);
-                    }
-                } else {
-                    const float inv = mx_inv_scale(byte);
-#pragma unroll
-                    for (int e = 0; e < N; ++e) w |= mx_quant(mx_clamp(f[k][e], maxf), inv) << (4 * e);
-                }
-            }
-            // plain stores: the payload stays in L2 / the Infinity Cache for its reader
-            if constexpr (N == 4) reinterpret_cast<uint16_t*>(pay + b * kMxBlockBytes)[sub] = (uint16_t)w;
-            else reinterpret_cast<uint32_t*>(pay + b * kMxBlockBytes)[sub] = w;
-            if (sub == 0) {
-                seg[b] = (uint8_t)byte;
-                if (last && b == nb - 1) {  // slack of both regions, zero
-                    for (int64_t q = nb; q < sbytes - bb; ++q) seg[q] = 0;
-                    if ((bb + nb) * kMxBlockBytes < pbytes)
-                        *reinterpret_cast<uint4*>(pay + nb * kMxBlockBytes) = make_uint4(0u, 0u, 0u, 0u);
-                }
-            }
+            uint32_t byte, w;
+            mx_encode_lane<N, mx_round(HW, SR)>(f[k], am, maxf, byte, w,
+                                                (uint32_t)((int64_t)c * cs + (bb + b0 + k * BW) * kMxBlock + lane * N), k0, k1);
+            mx_store_lane<N>(seg, pay, b, sub, byte, w, nb, bb, last, sbytes, pbytes);
         }
     }
 }
@@ -254,40 +203,7 @@ __global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_kernel(const uint8
     const float pf = (float)p, maxf = T::init_max();
     for (int64_t b = bb + (int64_t)blockIdx.x * kBlock + threadIdx.x; b < be; b += (int64_t)gridDim.x * kBlock) {
         float x[kMxBlock];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {  // eight elements (one payload word) of every segment at a time
-            float s[8][BY];
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-#pragma unroll
-                for (int y = 0; y < BY; ++y) s[e][y] = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {  // p <= 2 * BY
-                uint32_t w[BY], sb[BY];
-#pragma unroll
-                for (int y = 0; y < BY; ++y) {
-                    const int cc = r * BY + y < p ? r * BY + y : p - 1;
-                    const uint8_t* seg = in + (int64_t)cc * segb;
-                    sb[y] = seg[b];
-                    w[y] = reinterpret_cast<const uint32_t*>(seg + sbytes + b * kMxBlockBytes)[q];
-                }
-#pragma unroll
-                for (int y = 0; y < BY; ++y) {
-                    if (r * BY + y >= p) break;
-                    uint32_t u[8];
-                    mx_decode<T, HW, 4>(w[y], sb[y], u);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) s[e][y] = s[e][y] + from_stored_bits<T>(u[e]);
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                tree_finish<BY>(s[e]);
-                const int64_t j = b * kMxBlock + q * 8 + e;
-                // the reduced value as stored in T; padding past cs stays +0, as the encoder sees it
-                x[q * 8 + e] = j < cs ? as_stored<T>(average ? s[e][0] / pf : s[e][0]) : 0.0f;
-            }
-        }
+        mx_reduce_block<T, BY, HW>(in, segb, sbytes, b, p, average, pf, cs, x);
         if constexpr (STORE) {
             if (vec && (b + 1) * kMxBlock <= cs) {
 #pragma unroll
@@ -306,13 +222,7 @@ __global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_kernel(const uint8
         uint32_t byte, w[4];
         if constexpr (SR) mx_encode_block_sr(x, maxf, j_chunk + (uint32_t)b * kMxBlock, k0, k1, byte, w);
         else mx_encode<HW>(x, maxf, byte, w);
-        out_seg[b] = (uint8_t)byte;
-        *reinterpret_cast<uint4*>(pay_out + b * kMxBlockBytes) = make_uint4(w[0], w[1], w[2], w[3]);
-        if (b == nb - 1) {
-            for (int64_t k = nb; k < sbytes; ++k) out_seg[k] = 0;
-            if (nb * kMxBlockBytes < pbytes)
-                *reinterpret_cast<uint4*>(pay_out + nb * kMxBlockBytes) = make_uint4(0u, 0u, 0u, 0u);
-        }
+        mx_store_block(out_seg, pay_out, b, byte, w, nb, sbytes, pbytes);
     }
 }
 
@@ -384,99 +294,25 @@ __global__ __launch_bounds__(kBlock) void mxfp4_encode_ef_kernel(const typename 
         const int64_t b0 = t * TB;
         const bool full = (b0 + TB) * kMxBlock <= cs;
         float f[R][N], r[R][N];
-        if (vecx && full) {
-            uint4 raw[R];
-#pragma unroll
-            for (int k = 0; k < R; ++k) raw[k] = nt_load16(src + (b0 + k * BW) * kMxBlock + lane * N);
-#pragma unroll
-            for (int k = 0; k < R; ++k) unpack16<T>(raw[k], f[k]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < R; ++k)
-#pragma unroll
-                for (int e = 0; e < N; ++e) {
-                    const int64_t j = (b0 + k * BW) * kMxBlock + lane * N + e;
-                    f[k][e] = j < cs ? T::to_f(src[j]) : 0.0f;
-                }
-        }
-        if (vecr && full) {
-#pragma unroll
-            for (int k = 0; k < R; ++k)
-#pragma unroll
-                for (int h = 0; h < N / 4; ++h) {
-                    const float* q = rsd + (b0 + k * BW) * kMxBlock + lane * N + 4 * h;
-                    const uint4 u = NT ? nt_load16(q) : *reinterpret_cast<const uint4*>(q);
-                    r[k][4 * h] = __uint_as_float(u.x);
-                    r[k][4 * h + 1] = __uint_as_float(u.y);
-                    r[k][4 * h + 2] = __uint_as_float(u.z);
-                    r[k][4 * h + 3] = __uint_as_float(u.w);
-                }
-        } else {
-#pragma unroll
-            for (int k = 0; k < R; ++k)
-#pragma unroll
-                for (int e = 0; e < N; ++e) {
-                    const int64_t j = (b0 + k * BW) * kMxBlock + lane * N + e;
-                    r[k][e] = j < cs ? rsd[j] : 0.0f;
-                }
-        }
+        mx_load_tile<T, true>(src, b0, lane, cs, vecx && full, f);
+        mx_load_tile<F32, NT>(rsd, b0, lane, cs, vecr && full, r);
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            uint32_t am = 0;
 #pragma unroll
-            for (int e = 0; e < N; ++e) {
-                r[k][e] = mx_ef_sum(f[k][e], r[k][e]);  // v, and below the new residual
-                am = max(am, __float_as_uint(r[k][e]) & 0x7fffffffu);
-            }
-#pragma unroll
-            for (int o = 1; o < G; o <<= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, kWave));
+            for (int e = 0; e < N; ++e) r[k][e] = mx_ef_sum(f[k][e], r[k][e]);  // v, and below the new residual
+            const uint32_t am = mx_block_amax<N>(r[k]);
             const int64_t b = b0 + k * BW + lb;
             if (b >= nb) continue;
-            uint32_t byte = kMxNanScale, w = 0;
-            if (am <= 0x7f800000u) {
-                byte = mx_scale_byte(min(am, __float_as_uint(maxf)));
-                if constexpr (HW) {
-                    const float scale = __uint_as_float(byte << 23);
-                    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(r[k][0], maxf), mx_clamp(r[k][1], maxf), scale, 0);
-                    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(r[k][2], maxf), mx_clamp(r[k][3], maxf), scale, 1);
-                    if constexpr (N == 8) {
-                        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(r[k][4], maxf), mx_clamp(r[k][5], maxf), scale, 2);
-                        w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx_clamp(r[k][6], maxf), mx_clamp(r[k][7], maxf), scale, 3);
-                    }
-                } else {
-                    const float inv = mx_inv_scale(byte);
-#pragma unroll
-                    for (int e = 0; e < N; ++e) w |= mx_quant(mx_clamp(r[k][e], maxf), inv) << (4 * e);
-                }
+            uint32_t byte, w;
+            mx_encode_lane<N, mx_round(HW)>(r[k], am, maxf, byte, w);
+            if (byte != kMxNanScale) {
                 mx_residual<T, HW, N>(r[k], &w, byte, maxf);
             } else {  // a NaN block: the state is reset
 #pragma unroll
                 for (int e = 0; e < N; ++e) r[k][e] = 0.0f;
             }
-            if constexpr (N == 4) reinterpret_cast<uint16_t*>(pay + b * kMxBlockBytes)[sub] = (uint16_t)w;
-            else reinterpret_cast<uint32_t*>(pay + b * kMxBlockBytes)[sub] = w;
-            if (sub == 0) {
-                seg[b] = (uint8_t)byte;
-                if (b == nb - 1) {  // slack of both regions, zero
-                    for (int64_t q = nb; q < sbytes; ++q) seg[q] = 0;
-                    if (nb * kMxBlockBytes < pbytes)
-                        *reinterpret_cast<uint4*>(pay + nb * kMxBlockBytes) = make_uint4(0u, 0u, 0u, 0u);
-                }
-            }
-            const int64_t j0 = (b0 + k * BW) * kMxBlock + lane * N;
-            if (vecr && full) {
-#pragma unroll
-                for (int h = 0; h < N / 4; ++h) {
-                    const uint4 u = make_uint4(__float_as_uint(r[k][4 * h]), __float_as_uint(r[k][4 * h + 1]),
-                                               __float_as_uint(r[k][4 * h + 2]), __float_as_uint(r[k][4 * h + 3]));
-                    if constexpr (NT) nt_store16(u, rsd + j0 + 4 * h);
-                    else *reinterpret_cast<uint4*>(rsd + j0 + 4 * h) = u;
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < N; ++e)
-                    if (j0 + e < cs) rsd[j0 + e] = r[k][e];
-            }
+            mx_store_lane<N>(seg, pay, b, sub, byte, w, nb, 0, true, sbytes, pbytes);
+            mx_store_row<NT>(rsd, (b0 + k * BW) * kMxBlock + lane * N, cs, vecr && full, r[k]);
         }
     }
 }
@@ -495,88 +331,27 @@ __global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_ef_kernel(const ui
     const float pf = (float)p, maxf = T::init_max();
     for (int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; b < nb; b += (int64_t)gridDim.x * kBlock) {
         float x[kMxBlock];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float s[8][BY];
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-#pragma unroll
-                for (int y = 0; y < BY; ++y) s[e][y] = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {  // p <= 2 * BY
-                uint32_t w[BY], sb[BY];
-#pragma unroll
-                for (int y = 0; y < BY; ++y) {
-                    const int cc = r * BY + y < p ? r * BY + y : p - 1;
-                    const uint8_t* seg = in + (int64_t)cc * segb;
-                    sb[y] = seg[b];
-                    w[y] = reinterpret_cast<const uint32_t*>(seg + sbytes + b * kMxBlockBytes)[q];
-                }
-#pragma unroll
-                for (int y = 0; y < BY; ++y) {
-                    if (r * BY + y >= p) break;
-                    uint32_t u[8];
-                    mx_decode<T, HW, 4>(w[y], sb[y], u);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) s[e][y] = s[e][y] + from_stored_bits<T>(u[e]);
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                tree_finish<BY>(s[e]);
-                const int64_t j = b * kMxBlock + q * 8 + e;
-                x[q * 8 + e] = j < cs ? as_stored<T>(average ? s[e][0] / pf : s[e][0]) : 0.0f;
-            }
-        }
+        mx_reduce_block<T, BY, HW>(in, segb, sbytes, b, p, average, pf, cs, x);
         const bool whole = vec && (b + 1) * kMxBlock <= cs;
-        float* rb = res + b * kMxBlock;
-        if (whole) {
-#pragma unroll
-            for (int k = 0; k < kMxBlock / 4; ++k) {
-                const uint4 u = *reinterpret_cast<const uint4*>(rb + 4 * k);
-                x[4 * k] = mx_ef_sum(x[4 * k], __uint_as_float(u.x));
-                x[4 * k + 1] = mx_ef_sum(x[4 * k + 1], __uint_as_float(u.y));
-                x[4 * k + 2] = mx_ef_sum(x[4 * k + 2], __uint_as_float(u.z));
-                x[4 * k + 3] = mx_ef_sum(x[4 * k + 3], __uint_as_float(u.w));
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < kMxBlock; ++e)
-                x[e] = mx_ef_sum(x[e], b * kMxBlock + e < cs ? rb[e] : 0.0f);
-        }
+        mx_add_residual(x, res, b, cs, whole);
         uint32_t byte, w[4];
         mx_encode<HW>(x, maxf, byte, w);
-        out_seg[b] = (uint8_t)byte;
-        *reinterpret_cast<uint4*>(pay_out + b * kMxBlockBytes) = make_uint4(w[0], w[1], w[2], w[3]);
-        if (b == nb - 1) {
-            for (int64_t k = nb; k < sbytes; ++k) out_seg[k] = 0;
-            if (nb * kMxBlockBytes < pbytes)
-                *reinterpret_cast<uint4*>(pay_out + nb * kMxBlockBytes) = make_uint4(0u, 0u, 0u, 0u);
-        }
+        mx_store_block(out_seg, pay_out, b, byte, w, nb, sbytes, pbytes);
         if (byte != kMxNanScale) {
             mx_residual<T, HW, kMxBlock>(x, w, byte, maxf);
         } else {
 #pragma unroll
             for (int e = 0; e < kMxBlock; ++e) x[e] = 0.0f;
         }
-        if (whole) {
-#pragma unroll
-            for (int k = 0; k < kMxBlock / 4; ++k)
-                *reinterpret_cast<uint4*>(rb + 4 * k) =
-                    make_uint4(__float_as_uint(x[4 * k]), __float_as_uint(x[4 * k + 1]), __float_as_uint(x[4 * k + 2]),
-                               __float_as_uint(x[4 * k + 3]));
-        } else {
-#pragma unroll
-            for (int e = 0; e < kMxBlock; ++e)
-                if (b * kMxBlock + e < cs) rb[e] = x[e];
-        }
+        mx_store_row<false>(res, b * kMxBlock, cs, whole, x);
     }
 }
 
 // ------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------
-// mx_hw() and mx_grid(): mxfp4_device.hpp
+// mx_hw(), mx_grid(), the dispatch helpers (mx_with_dtype / _bool / _by) and the shared
+// argument checks: mxfp4_device.hpp
 
 // A block range [bb, be) of a chunk of cs elements as the range entries take it: bb a
 // multiple of the granule in [0, nb], be in [bb, nb] and either nb or a multiple of it.
@@ -596,10 +371,9 @@ template <typename T>
 static int mx_compress_impl(const void* input, int in_num_elem, int cs, int p, uint8_t* out, size_t out_bytes,
                             int target, int bb, int be, const uint64_t* key, hipStream_t s) {
     using S = typename T::storage;
-    if (p <= 0 || p > 65535 || cs < 0 || in_num_elem < 0 || target < -1 || target >= p || !out || !input)
+    if (!mx_counts_ok(p, cs, kMxGridChunks) || in_num_elem < 0 || target < -1 || target >= p || !out || !input)
         return BAGUA_ERR_INVALID_ARG;
-    if (out_bytes < (size_t)p * (size_t)mx_segment_bytes(cs)) return BAGUA_ERR_INVALID_ARG;
-    if ((uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;  // payload words and the 16-B slack store are aligned stores
+    if (!mx_holds(out_bytes, cs, p) || !mx_aligned(out, 16)) return BAGUA_ERR_INVALID_ARG;
     if (!mx_range(cs, bb, be)) return BAGUA_ERR_INVALID_ARG;
     if (bb == be) return BAGUA_OK;
     // a wave tile is 8 KiB of input, a workgroup four of them; the grid covers the range
@@ -608,33 +382,22 @@ static int mx_compress_impl(const void* input, int in_num_elem, int cs, int p, u
     const dim3 grid(mx_grid(((int64_t)(be - bb) + kTileBlocks - 1) / kTileBlocks, kWavesPerBlock, nact,
                             "BAGUA_TUNE_MX_ENCODE_BLOCKS"),
                     nact);
-    if (key)  // stochastic rounding: the arithmetic alone (MXFP4.md, "The hardware conversion")
-        launch(mxfp4_encode_kernel<T, false, true>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
-               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be, (uint32_t)*key,
-               (uint32_t)(*key >> 32));
-    else if (mx_hw())
-        launch(mxfp4_encode_kernel<T, true, false>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
-               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be, 0u, 0u);
-    else
-        launch(mxfp4_encode_kernel<T, false, false>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
-               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be, 0u, 0u);
+    auto go = [&](auto kern) {
+        launch(kern, grid, dim3(kBlock), 0, s, static_cast<const S*>(input), (int64_t)in_num_elem, (int64_t)cs, target,
+               out, (int64_t)bb, (int64_t)be, key ? (uint32_t)*key : 0u, key ? (uint32_t)(*key >> 32) : 0u);
+    };
+    if (key) go(mxfp4_encode_kernel<T, false, true>);  // stochastic: the arithmetic alone (MXFP4.md, "The hardware conversion")
+    else if (mx_hw()) go(mxfp4_encode_kernel<T, true, false>);
+    else go(mxfp4_encode_kernel<T, false, false>);
     return check_launch();
-}
-
-template <typename T, bool HW>
-static void mx_launch_decode(const dim3& grid, bool nt, const uint8_t* in, int64_t cs, typename T::storage* out,
-                             int64_t bb, int64_t be, hipStream_t s) {
-    if (nt) launch(mxfp4_decode_kernel<T, HW, true>, grid, dim3(kBlock), 0, s, in, cs, out, bb, be);
-    else launch(mxfp4_decode_kernel<T, HW, false>, grid, dim3(kBlock), 0, s, in, cs, out, bb, be);
 }
 
 template <typename T>
 static int mx_decompress_impl(const uint8_t* in, size_t in_bytes, int cs, int p, void* out, int bb, int be,
                               hipStream_t s) {
     using S = typename T::storage;
-    if (p <= 0 || p > 65535 || cs < 0 || !in || !out) return BAGUA_ERR_INVALID_ARG;
-    if (in_bytes < (size_t)p * (size_t)mx_segment_bytes(cs)) return BAGUA_ERR_INVALID_ARG;
-    if ((uintptr_t)in % 4) return BAGUA_ERR_INVALID_ARG;  // payload read as 2- and 4-B words
+    if (!mx_counts_ok(p, cs, kMxGridChunks) || !in || !out) return BAGUA_ERR_INVALID_ARG;
+    if (!mx_holds(in_bytes, cs, p) || !mx_aligned(in, 4)) return BAGUA_ERR_INVALID_ARG;
     if (!mx_range(cs, bb, be)) return BAGUA_ERR_INVALID_ARG;
     if (bb == be) return BAGUA_OK;
     // store policy by the bucket's size (not the range's), as the 1-bit decode's (onebit.hip): past the
@@ -645,35 +408,24 @@ static int mx_decompress_impl(const uint8_t* in, size_t in_bytes, int cs, int p,
     const int64_t last = std::min(((int64_t)cs + N - 1) / N, (int64_t)be * (kMxBlock / N));
     const int64_t nvec = last - (int64_t)bb * (kMxBlock / N);  // the range's 16-B output vectors
     const dim3 grid(mx_grid(nvec, kBlock * kMxDecodeVecs, p, "BAGUA_TUNE_MX_DECODE_BLOCKS"), p);
-    if (mx_hw()) mx_launch_decode<T, true>(grid, nt, in, (int64_t)cs, static_cast<S*>(out), bb, be, s);
-    else mx_launch_decode<T, false>(grid, nt, in, (int64_t)cs, static_cast<S*>(out), bb, be, s);
+    mx_with_bool(mx_hw(), [&](auto hw) {
+        mx_with_bool(nt, [&](auto nts) {
+            launch(mxfp4_decode_kernel<T, decltype(hw)::value, decltype(nts)::value>, grid, dim3(kBlock), 0, s, in,
+                   (int64_t)cs, static_cast<S*>(out), (int64_t)bb, (int64_t)be);
+        });
+    });
     return check_launch();
 }
 
-template <typename T, int BY, bool HW>
-static void mx_launch_reduce(int blocks, const uint8_t* in, int64_t cs, int p, int average,
-                             typename T::storage* chunk, uint8_t* seg, int64_t bb, int64_t be, uint32_t j_chunk,
-                             const uint64_t* key, hipStream_t s) {
-    if (key)  // stochastic re-encode (never storing); the decode of the received segments is the plain one
-        launch(mxfp4_reduce_encode_kernel<T, BY, HW, false, true>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p,
-               average, chunk, seg, bb, be, j_chunk, (uint32_t)*key, (uint32_t)(*key >> 32));
-    else if (chunk)
-        launch(mxfp4_reduce_encode_kernel<T, BY, HW, true, false>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p,
-               average, chunk, seg, bb, be, 0u, 0u, 0u);
-    else
-        launch(mxfp4_reduce_encode_kernel<T, BY, HW, false, false>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p,
-               average, chunk, seg, bb, be, 0u, 0u, 0u);
-}
-
-template <typename T, bool HW>
-static void mx_dispatch_reduce(int blocks, const uint8_t* in, int64_t cs, int p, int average,
-                               typename T::storage* chunk, uint8_t* seg, int64_t bb, int64_t be, uint32_t j_chunk,
-                               const uint64_t* key, hipStream_t s) {
-    switch (reduce_by(p)) {
-        case 2: mx_launch_reduce<T, 2, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, j_chunk, key, s); break;
-        case 4: mx_launch_reduce<T, 4, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, j_chunk, key, s); break;
-        default: mx_launch_reduce<T, 8, HW>(blocks, in, cs, p, average, chunk, seg, bb, be, j_chunk, key, s); break;
-    }
+// What the two middle steps check alike, in their order of precedence; the error-feedback one
+// checks its residual first, which gives the code of the first line here.
+static int mx_check_middle(const uint8_t* recv, size_t recv_bytes, int cs, int p, const uint8_t* out, size_t out_bytes,
+                           int target) {
+    if (!mx_counts_ok(p, cs) || target < 0 || target >= p || !recv || !out) return BAGUA_ERR_INVALID_ARG;
+    if (p > kMaxFusedChunks) return BAGUA_ERR_UNSUPPORTED;  // caller runs decompress + reduce + compress
+    if (!mx_holds(recv_bytes, cs, p) || !mx_holds(out_bytes, cs, p)) return BAGUA_ERR_INVALID_ARG;
+    if (!mx_aligned(recv, 4) || !mx_aligned(out, 16)) return BAGUA_ERR_INVALID_ARG;
+    return BAGUA_OK;
 }
 
 template <typename T>
@@ -681,39 +433,39 @@ static int mx_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, int
                                      uint8_t* out, size_t out_bytes, int target, int bb, int be, const uint64_t* key,
                                      hipStream_t s) {
     using S = typename T::storage;
-    if (p <= 0 || cs < 0 || target < 0 || target >= p || !recv || !out) return BAGUA_ERR_INVALID_ARG;
-    if (p > kMaxFusedChunks) return BAGUA_ERR_UNSUPPORTED;  // caller runs decompress + reduce + compress
-    const size_t segb = (size_t)mx_segment_bytes(cs);
-    if (recv_bytes < (size_t)p * segb || out_bytes < (size_t)p * segb) return BAGUA_ERR_INVALID_ARG;
-    if ((uintptr_t)recv % 4 || (uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;
+    if (const int e = mx_check_middle(recv, recv_bytes, cs, p, out, out_bytes, target)) return e;
     if (!mx_range(cs, bb, be)) return BAGUA_ERR_INVALID_ARG;
     if (bb == be) return BAGUA_OK;
     S* chunk = tensor ? static_cast<S*>(tensor) + (int64_t)target * cs : nullptr;  // nullptr: not stored
-    uint8_t* seg = out + (size_t)target * segb;
+    uint8_t* seg = out + (size_t)target * (size_t)mx_segment_bytes(cs);
     const int blocks = mx_grid(be - bb, kBlock, 1, "BAGUA_TUNE_MX_MIDDLE_BLOCKS");
-    const uint32_t jc = (uint32_t)((int64_t)target * cs);  // index of the own chunk's first element
-    if (mx_hw()) mx_dispatch_reduce<T, true>(blocks, recv, (int64_t)cs, p, average, chunk, seg, bb, be, jc, key, s);
-    else mx_dispatch_reduce<T, false>(blocks, recv, (int64_t)cs, p, average, chunk, seg, bb, be, jc, key, s);
+    const uint32_t jc = key ? (uint32_t)((int64_t)target * cs) : 0u;  // index of the own chunk's first element
+    mx_with_by(p, [&](auto by) {
+        mx_with_bool(mx_hw(), [&](auto hw) {
+            constexpr int BY = decltype(by)::value;
+            constexpr bool HW = decltype(hw)::value;
+            auto go = [&](auto kern) {
+                launch(kern, dim3(blocks), dim3(kBlock), 0, s, recv, (int64_t)cs, p, average, chunk, seg, (int64_t)bb,
+                       (int64_t)be, jc, key ? (uint32_t)*key : 0u, key ? (uint32_t)(*key >> 32) : 0u);
+            };
+            // stochastic re-encode (never storing); the decode of the received segments is the plain one
+            if (key) go(mxfp4_reduce_encode_kernel<T, BY, HW, false, true>);
+            else if (chunk) go(mxfp4_reduce_encode_kernel<T, BY, HW, true, false>);
+            else go(mxfp4_reduce_encode_kernel<T, BY, HW, false, false>);
+        });
+    });
     return check_launch();
 }
 
 // ---- error feedback ----
-template <typename T, bool HW>
-static void mx_launch_encode_ef(const dim3& grid, bool nt, const typename T::storage* in, int64_t cs, float* res,
-                                uint8_t* out, hipStream_t s) {
-    if (nt) launch(mxfp4_encode_ef_kernel<T, HW, true>, grid, dim3(kBlock), 0, s, in, cs, res, out);
-    else launch(mxfp4_encode_ef_kernel<T, HW, false>, grid, dim3(kBlock), 0, s, in, cs, res, out);
-}
-
 template <typename T>
 static int mx_compress_ef_impl(const void* input, int in_num_elem, int cs, int p, uint8_t* out, size_t out_bytes,
                                int target, float* residual, hipStream_t s) {
     using S = typename T::storage;
-    if (p <= 0 || p > 65535 || cs < 0 || target != -1 || !out || !input) return BAGUA_ERR_INVALID_ARG;
+    if (!mx_counts_ok(p, cs, kMxGridChunks) || target != -1 || !out || !input) return BAGUA_ERR_INVALID_ARG;
     if ((int64_t)in_num_elem != (int64_t)cs * p) return BAGUA_ERR_INVALID_ARG;  // every chunk fully valid
-    if (!residual || (uintptr_t)residual % 4) return BAGUA_ERR_INVALID_ARG;
-    if (out_bytes < (size_t)p * (size_t)mx_segment_bytes(cs)) return BAGUA_ERR_INVALID_ARG;
-    if ((uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;
+    if (!mx_residual_ok(residual)) return BAGUA_ERR_INVALID_ARG;
+    if (!mx_holds(out_bytes, cs, p) || !mx_aligned(out, 16)) return BAGUA_ERR_INVALID_ARG;
     if (cs == 0) return BAGUA_OK;
     constexpr int64_t kTileElems = kMxItemBytes * kWave / (int64_t)sizeof(S);
     const dim3 grid(mx_grid(((int64_t)cs + kTileElems - 1) / kTileElems, kWavesPerBlock, p, "BAGUA_TUNE_MX_ENCODE_BLOCKS"),
@@ -727,41 +479,29 @@ static int mx_compress_ef_impl(const void* input, int in_num_elem, int cs, int p
     // BAGUA_MX_EF_RESIDUAL_NT=1 / 0 forces either (A/B).
     const int env = tune_int("BAGUA_MX_EF_RESIDUAL_NT", -1);
     const bool nt = env >= 0 ? env != 0 : (int64_t)cs * p * (4 + (int64_t)sizeof(S)) > ((int64_t)256 << 20);
-    if (mx_hw()) mx_launch_encode_ef<T, true>(grid, nt, static_cast<const S*>(input), (int64_t)cs, residual, out, s);
-    else mx_launch_encode_ef<T, false>(grid, nt, static_cast<const S*>(input), (int64_t)cs, residual, out, s);
+    mx_with_bool(mx_hw(), [&](auto hw) {
+        mx_with_bool(nt, [&](auto ntr) {
+            launch(mxfp4_encode_ef_kernel<T, decltype(hw)::value, decltype(ntr)::value>, grid, dim3(kBlock), 0, s,
+                   static_cast<const S*>(input), (int64_t)cs, residual, out);
+        });
+    });
     return check_launch();
-}
-
-template <typename T, bool HW>
-static void mx_dispatch_reduce_ef(int blocks, const uint8_t* in, int64_t cs, int p, int average, float* res,
-                                  uint8_t* seg, hipStream_t s) {
-    switch (reduce_by(p)) {
-        case 2:
-            launch(mxfp4_reduce_encode_ef_kernel<T, 2, HW>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average, res, seg);
-            break;
-        case 4:
-            launch(mxfp4_reduce_encode_ef_kernel<T, 4, HW>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average, res, seg);
-            break;
-        default:
-            launch(mxfp4_reduce_encode_ef_kernel<T, 8, HW>, dim3(blocks), dim3(kBlock), 0, s, in, cs, p, average, res, seg);
-            break;
-    }
 }
 
 template <typename T>
 static int mx_reduce_requantize_ef_impl(const uint8_t* recv, size_t recv_bytes, int cs, int p, int average,
                                         uint8_t* out, size_t out_bytes, int target, float* residual, hipStream_t s) {
-    if (p <= 0 || cs < 0 || target < 0 || target >= p || !recv || !out) return BAGUA_ERR_INVALID_ARG;
-    if (!residual || (uintptr_t)residual % 4) return BAGUA_ERR_INVALID_ARG;
-    if (p > kMaxFusedChunks) return BAGUA_ERR_UNSUPPORTED;  // caller runs decompress + reduce + compress_ef
-    const size_t segb = (size_t)mx_segment_bytes(cs);
-    if (recv_bytes < (size_t)p * segb || out_bytes < (size_t)p * segb) return BAGUA_ERR_INVALID_ARG;
-    if ((uintptr_t)recv % 4 || (uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;
+    if (!mx_residual_ok(residual)) return BAGUA_ERR_INVALID_ARG;
+    if (const int e = mx_check_middle(recv, recv_bytes, cs, p, out, out_bytes, target)) return e;
     if (cs == 0) return BAGUA_OK;
-    uint8_t* seg = out + (size_t)target * segb;
+    uint8_t* seg = out + (size_t)target * (size_t)mx_segment_bytes(cs);
     const int blocks = mx_grid(mx_blocks(cs), kBlock, 1, "BAGUA_TUNE_MX_MIDDLE_BLOCKS");
-    if (mx_hw()) mx_dispatch_reduce_ef<T, true>(blocks, recv, (int64_t)cs, p, average, residual, seg, s);
-    else mx_dispatch_reduce_ef<T, false>(blocks, recv, (int64_t)cs, p, average, residual, seg, s);
+    mx_with_by(p, [&](auto by) {
+        mx_with_bool(mx_hw(), [&](auto hw) {
+            launch(mxfp4_reduce_encode_ef_kernel<T, decltype(by)::value, decltype(hw)::value>, dim3(blocks),
+                   dim3(kBlock), 0, s, recv, (int64_t)cs, p, average, residual, seg);
+        });
+    });
     return check_launch();
 }
 
@@ -781,37 +521,20 @@ int bagua_mxfp4_ef_state_bytes(int chunk_size, int num_chunks, size_t* worker_by
 int bagua_mxfp4_compress_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
                             uint8_t* output, size_t output_bytes, int target_chunk, float* residual,
                             bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return mx_compress_ef_impl<F32>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                            target_chunk, residual, s);
-        case BAGUA_DTYPE_F16:
-            return mx_compress_ef_impl<F16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                            target_chunk, residual, s);
-        case BAGUA_DTYPE_BF16:
-            return mx_compress_ef_impl<BF16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                             target_chunk, residual, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return mx_with_dtype(dtype, [&](auto t) {
+        return mx_compress_ef_impl<decltype(t)>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
+                                                target_chunk, residual, static_cast<hipStream_t>(stream));
+    });
 }
 
 int bagua_mxfp4_reduce_requantize_ef(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
                                      int num_chunks, int average, uint8_t* output, size_t output_bytes,
                                      int target_chunk, float* residual, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return mx_reduce_requantize_ef_impl<F32>(input, input_bytes, chunk_size, num_chunks, average, output,
-                                                     output_bytes, target_chunk, residual, s);
-        case BAGUA_DTYPE_F16:
-            return mx_reduce_requantize_ef_impl<F16>(input, input_bytes, chunk_size, num_chunks, average, output,
-                                                     output_bytes, target_chunk, residual, s);
-        case BAGUA_DTYPE_BF16:
-            return mx_reduce_requantize_ef_impl<BF16>(input, input_bytes, chunk_size, num_chunks, average, output,
-                                                      output_bytes, target_chunk, residual, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return mx_with_dtype(dtype, [&](auto t) {
+        return mx_reduce_requantize_ef_impl<decltype(t)>(input, input_bytes, chunk_size, num_chunks, average, output,
+                                                         output_bytes, target_chunk, residual,
+                                                         static_cast<hipStream_t>(stream));
+    });
 }
 
 size_t bagua_mxfp4_compressed_bytes(int chunk_size, int num_chunks) {
@@ -823,48 +546,26 @@ size_t bagua_mxfp4_compressed_bytes(int chunk_size, int num_chunks) {
 static int mx_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
                        uint8_t* output, size_t output_bytes, int target_chunk, int bb, int be, const uint64_t* key,
                        hipStream_t s) {
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return mx_compress_impl<F32>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                         target_chunk, bb, be, key, s);
-        case BAGUA_DTYPE_F16:
-            return mx_compress_impl<F16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                         target_chunk, bb, be, key, s);
-        case BAGUA_DTYPE_BF16:
-            return mx_compress_impl<BF16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                          target_chunk, bb, be, key, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return mx_with_dtype(dtype, [&](auto t) {
+        return mx_compress_impl<decltype(t)>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
+                                             target_chunk, bb, be, key, s);
+    });
 }
 
 static int mx_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
                          void* output, int bb, int be, hipStream_t s) {
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return mx_decompress_impl<F32>(input, input_bytes, chunk_size, num_chunks, output, bb, be, s);
-        case BAGUA_DTYPE_F16:
-            return mx_decompress_impl<F16>(input, input_bytes, chunk_size, num_chunks, output, bb, be, s);
-        case BAGUA_DTYPE_BF16:
-            return mx_decompress_impl<BF16>(input, input_bytes, chunk_size, num_chunks, output, bb, be, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return mx_with_dtype(dtype, [&](auto t) {
+        return mx_decompress_impl<decltype(t)>(input, input_bytes, chunk_size, num_chunks, output, bb, be, s);
+    });
 }
 
 static int mx_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
                                 void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
                                 int bb, int be, const uint64_t* key, hipStream_t s) {
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return mx_reduce_requantize_impl<F32>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
-                                                  output_bytes, target_chunk, bb, be, key, s);
-        case BAGUA_DTYPE_F16:
-            return mx_reduce_requantize_impl<F16>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
-                                                  output_bytes, target_chunk, bb, be, key, s);
-        case BAGUA_DTYPE_BF16:
-            return mx_reduce_requantize_impl<BF16>(input, input_bytes, chunk_size, num_chunks, tensor, average,
-                                                   output, output_bytes, target_chunk, bb, be, key, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return mx_with_dtype(dtype, [&](auto t) {
+        return mx_reduce_requantize_impl<decltype(t)>(input, input_bytes, chunk_size, num_chunks, tensor, average,
+                                                      output, output_bytes, target_chunk, bb, be, key, s);
+    });
 }
 
 int bagua_mxfp4_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,

@@ -23,11 +23,14 @@
 //             L += d; R += d; t = d + W; W = t.  No payload is written or read.
 // Every intermediate is rounded to T exactly where the reference stores it, so the segment
 // and all four tensors equal the composed sequence byte for byte.
+// The block encode, the store of its result with the slack rule and the decode are the
+// steps of mxfp4_device.hpp (mx_block_amax, mx_encode_lane, mx_store_lane, mx_decode), shared with mxfp4.hip;
+// the four-tensor load keeps its own interleaved issue order (mxr_load_rows).
 //
 // kMxRingRows = 2: with four tensors the plain encode's eight vectors in flight would be 32
 // loads and 128 VGPRs of raw data.  Two rows are 8 loads and 128 B in flight per lane, what
 // the plain encode has, and keep the mix at 62 VGPRs for f32 and 95-108 for 16-bit T, 8 and
-// 4-5 waves per SIMD, where the 16-bit error-feedback encode, at 160-168, has 3 (the
+// 4-5 waves per SIMD, where the 16-bit error-feedback encode, at 159-166, has 3 (the
 // compiler's resource-usage remarks; MXFP4.md has the table).  Four rows would double the
 // bytes in flight per lane for half the waves at best: no more bytes in flight per CU.  One
 // row was not tried; neither count has been timed against the other.
@@ -98,27 +101,6 @@ __device__ __forceinline__ void mxr_load_rows(const typename T::storage* __restr
     }
 }
 
-// The lane's part of the plain block encode of the mixed values m: the block's amax over its
-// G lanes (every lane of the wave runs the shuffles), the scale byte and the lane's N nibbles.
-// A NaN block: 0xFF and a zero payload.
-template <typename T, bool HW>
-__device__ __forceinline__ void mxr_encode_row(const float (&m)[Vec<T>::N], float maxf, uint32_t& byte,
-                                               uint32_t& wd) {
-    constexpr int N = Vec<T>::N;
-    constexpr int G = kMxBlock / N;
-    uint32_t am = 0;
-#pragma unroll
-    for (int e = 0; e < N; ++e) am = max(am, __float_as_uint(m[e]) & 0x7fffffffu);
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, kWave));
-    byte = kMxNanScale;
-    wd = 0;
-    if (am <= 0x7f800000u) {
-        byte = mx_scale_byte(min(am, __float_as_uint(maxf)));
-        wd = mx_quant_lane<N, HW>(m, byte, maxf);
-    }
-}
-
 // ------------------------------------------------------------------------
 // mix + encode: t is read, never written
 // ------------------------------------------------------------------------
@@ -149,21 +131,11 @@ __global__ __launch_bounds__(kBlock) void mxfp4_ring_mix_kernel(const typename T
             float m[N];
 #pragma unroll
             for (int e = 0; e < N; ++e) m[e] = mix<T>(ft[k][e], fl[k][e], fr[k][e], fw[k][e], f13, f53);
-            uint32_t byte, wd;
-            mxr_encode_row<T, HW>(m, maxf, byte, wd);
+            uint32_t byte, wd;  // the plain block encode of the mixed values
+            mx_encode_lane<N, mx_round(HW)>(m, mx_block_amax<N>(m), maxf, byte, wd);
             const int64_t b = b0 + k * BW + lb;
             if (b >= nb) continue;
-            // plain stores: the payload stays in L2 / the Infinity Cache for its reader
-            if constexpr (N == 4) reinterpret_cast<uint16_t*>(pay + b * kMxBlockBytes)[sub] = (uint16_t)wd;
-            else reinterpret_cast<uint32_t*>(pay + b * kMxBlockBytes)[sub] = wd;
-            if (sub == 0) {
-                out[b] = (uint8_t)byte;
-                if (b == nb - 1) {  // slack of both regions, zero
-                    for (int64_t q = nb; q < sbytes; ++q) out[q] = 0;
-                    if (nb * kMxBlockBytes < pbytes)
-                        *reinterpret_cast<uint4*>(pay + nb * kMxBlockBytes) = make_uint4(0u, 0u, 0u, 0u);
-                }
-            }
+            mx_store_lane<N>(out, pay, b, sub, byte, wd, nb, 0, true, sbytes, pbytes);
         }
     }
 }
@@ -198,8 +170,8 @@ __global__ __launch_bounds__(kBlock) void mxfp4_ring_one_rank_kernel(typename T:
             float m[N];
 #pragma unroll
             for (int e = 0; e < N; ++e) m[e] = mix<T>(ft[k][e], fl[k][e], fr[k][e], fw[k][e], f13, f53);
-            uint32_t byte, wd;
-            mxr_encode_row<T, HW>(m, maxf, byte, wd);
+            uint32_t byte, wd;  // the plain block encode of the mixed values
+            mx_encode_lane<N, mx_round(HW)>(m, mx_block_amax<N>(m), maxf, byte, wd);
             if (b0 + k * BW + lb >= nb) continue;
             uint32_t u[N];  // the lane's own elements as every peer would decode them
             mx_decode<T, HW, N / 2>(wd, byte, u);
@@ -312,7 +284,10 @@ __global__ __launch_bounds__(kBlock) void mxfp4_ring_apply_kernel(const uint8_t*
 // ------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------
-static bool mxr_aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+// the four tensors take 16-B vector accesses
+static bool mxr_aligned16(const void* a, const void* b, const void* c, const void* d) {
+    return mx_aligned(a, 16) && mx_aligned(b, 16) && mx_aligned(c, 16) && mx_aligned(d, 16);
+}
 
 // Store policy of the apply and the one-rank kernel by what they write, four tensors: past
 // the 256 MiB Infinity Cache the dirty lines cannot stay on chip and the stores are
@@ -335,16 +310,14 @@ static int mxr_mix_impl(const void* t, const void* l, const void* r, const void*
                         size_t out_bytes, hipStream_t s) {
     using S = typename T::storage;
     if (!t || !l || !r || !w || !out || n <= 0) return BAGUA_ERR_INVALID_ARG;
-    if (out_bytes < (size_t)mx_segment_bytes(n) || (uintptr_t)out % 16) return BAGUA_ERR_INVALID_ARG;
-    if (!mxr_aligned16(t) || !mxr_aligned16(l) || !mxr_aligned16(r) || !mxr_aligned16(w)) return BAGUA_ERR_UNSUPPORTED;
+    if (!mx_holds(out_bytes, n, 1) || !mx_aligned(out, 16)) return BAGUA_ERR_INVALID_ARG;
+    if (!mxr_aligned16(t, l, r, w)) return BAGUA_ERR_UNSUPPORTED;
     const float f13 = mx_ring_factor(T::kDtype, 1.0 / 3.0), f53 = mx_ring_factor(T::kDtype, -5.0 / 3.0);
     const dim3 grid(mxr_tile_grid<T>(n, "BAGUA_TUNE_MX_RING_MIX_BLOCKS"));
-    auto go = [&](auto kern) {
-        launch(kern, grid, dim3(kBlock), 0, s, static_cast<const S*>(t), static_cast<const S*>(l),
-               static_cast<const S*>(r), static_cast<const S*>(w), (int64_t)n, f13, f53, out);
-    };
-    if (mx_hw()) go(mxfp4_ring_mix_kernel<T, true>);
-    else go(mxfp4_ring_mix_kernel<T, false>);
+    mx_with_bool(mx_hw(), [&](auto hw) {
+        launch(mxfp4_ring_mix_kernel<T, decltype(hw)::value>, grid, dim3(kBlock), 0, s, static_cast<const S*>(t),
+               static_cast<const S*>(l), static_cast<const S*>(r), static_cast<const S*>(w), (int64_t)n, f13, f53, out);
+    });
     return check_launch();
 }
 
@@ -352,21 +325,15 @@ template <typename T>
 static int mxr_one_rank_impl(void* t, void* w, void* l, void* r, int n, hipStream_t s) {
     using S = typename T::storage;
     if (!t || !w || !l || !r || n <= 0) return BAGUA_ERR_INVALID_ARG;
-    if (!mxr_aligned16(t) || !mxr_aligned16(w) || !mxr_aligned16(l) || !mxr_aligned16(r)) return BAGUA_ERR_UNSUPPORTED;
+    if (!mxr_aligned16(t, w, l, r)) return BAGUA_ERR_UNSUPPORTED;
     const float f13 = mx_ring_factor(T::kDtype, 1.0 / 3.0), f53 = mx_ring_factor(T::kDtype, -5.0 / 3.0);
     const dim3 grid(mxr_tile_grid<T>(n, "BAGUA_TUNE_MX_RING_ONE_RANK_BLOCKS"));
-    auto go = [&](auto kern) {
-        launch(kern, grid, dim3(kBlock), 0, s, static_cast<S*>(t), static_cast<S*>(w), static_cast<S*>(l),
-               static_cast<S*>(r), (int64_t)n, f13, f53);
-    };
-    const bool nt = mxr_nt_stores<T>(n);
-    if (mx_hw()) {
-        if (nt) go(mxfp4_ring_one_rank_kernel<T, true, true>);
-        else go(mxfp4_ring_one_rank_kernel<T, true, false>);
-    } else {
-        if (nt) go(mxfp4_ring_one_rank_kernel<T, false, true>);
-        else go(mxfp4_ring_one_rank_kernel<T, false, false>);
-    }
+    mx_with_bool(mx_hw(), [&](auto hw) {
+        mx_with_bool(mxr_nt_stores<T>(n), [&](auto nts) {
+            launch(mxfp4_ring_one_rank_kernel<T, decltype(hw)::value, decltype(nts)::value>, grid, dim3(kBlock), 0, s,
+                   static_cast<S*>(t), static_cast<S*>(w), static_cast<S*>(l), static_cast<S*>(r), (int64_t)n, f13, f53);
+        });
+    });
     return check_launch();
 }
 
@@ -375,24 +342,18 @@ static int mxr_apply_impl(const uint8_t* mine, const uint8_t* from_left, const u
                           int n, void* t, void* w, void* l, void* r, hipStream_t s) {
     using S = typename T::storage;
     if (!mine || !from_left || !from_right || !t || !w || !l || !r || n <= 0) return BAGUA_ERR_INVALID_ARG;
-    if (comp_bytes < (size_t)mx_segment_bytes(n)) return BAGUA_ERR_INVALID_ARG;
-    for (const uint8_t* p : {mine, from_left, from_right})
-        if ((uintptr_t)p % 4) return BAGUA_ERR_INVALID_ARG;  // payload read as 2- and 4-B words
-    if (!mxr_aligned16(t) || !mxr_aligned16(w) || !mxr_aligned16(l) || !mxr_aligned16(r)) return BAGUA_ERR_UNSUPPORTED;
+    if (!mx_holds(comp_bytes, n, 1)) return BAGUA_ERR_INVALID_ARG;
+    if (!mx_aligned(mine, 4) || !mx_aligned(from_left, 4) || !mx_aligned(from_right, 4)) return BAGUA_ERR_INVALID_ARG;
+    if (!mxr_aligned16(t, w, l, r)) return BAGUA_ERR_UNSUPPORTED;
     const int64_t nvec = ((int64_t)n + Vec<T>::N - 1) / Vec<T>::N;
     const dim3 grid(mx_grid(nvec, kBlock * kMxRingApplyVecs, 1, "BAGUA_TUNE_MX_RING_APPLY_BLOCKS"));
-    auto go = [&](auto kern) {
-        launch(kern, grid, dim3(kBlock), 0, s, mine, from_left, from_right, (int64_t)n, static_cast<S*>(t),
-               static_cast<S*>(w), static_cast<S*>(l), static_cast<S*>(r));
-    };
-    const bool nt = mxr_nt_stores<T>(n);
-    if (mx_hw()) {
-        if (nt) go(mxfp4_ring_apply_kernel<T, true, true>);
-        else go(mxfp4_ring_apply_kernel<T, true, false>);
-    } else {
-        if (nt) go(mxfp4_ring_apply_kernel<T, false, true>);
-        else go(mxfp4_ring_apply_kernel<T, false, false>);
-    }
+    mx_with_bool(mx_hw(), [&](auto hw) {
+        mx_with_bool(mxr_nt_stores<T>(n), [&](auto nts) {
+            launch(mxfp4_ring_apply_kernel<T, decltype(hw)::value, decltype(nts)::value>, grid, dim3(kBlock), 0, s, mine,
+                   from_left, from_right, (int64_t)n, static_cast<S*>(t), static_cast<S*>(w), static_cast<S*>(l),
+                   static_cast<S*>(r));
+        });
+    });
     return check_launch();
 }
 
@@ -404,43 +365,26 @@ extern "C" {
 
 int bagua_ring_mix_mxfp4(int dtype, const void* tensor, const void* left, const void* right, const void* weight,
                          int num_elem, uint8_t* output, size_t output_bytes, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32: return mxr_mix_impl<F32>(tensor, left, right, weight, num_elem, output, output_bytes, s);
-        case BAGUA_DTYPE_F16: return mxr_mix_impl<F16>(tensor, left, right, weight, num_elem, output, output_bytes, s);
-        case BAGUA_DTYPE_BF16:
-            return mxr_mix_impl<BF16>(tensor, left, right, weight, num_elem, output, output_bytes, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return mx_with_dtype(dtype, [&](auto t) {
+        return mxr_mix_impl<decltype(t)>(tensor, left, right, weight, num_elem, output, output_bytes,
+                                         static_cast<hipStream_t>(stream));
+    });
 }
 
 int bagua_ring_apply_mxfp4(int dtype, const uint8_t* mine, const uint8_t* from_left, const uint8_t* from_right,
                            size_t compressed_bytes, int num_elem, void* tensor, void* weight, void* left, void* right,
                            bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return mxr_apply_impl<F32>(mine, from_left, from_right, compressed_bytes, num_elem, tensor, weight, left,
-                                       right, s);
-        case BAGUA_DTYPE_F16:
-            return mxr_apply_impl<F16>(mine, from_left, from_right, compressed_bytes, num_elem, tensor, weight, left,
-                                       right, s);
-        case BAGUA_DTYPE_BF16:
-            return mxr_apply_impl<BF16>(mine, from_left, from_right, compressed_bytes, num_elem, tensor, weight, left,
-                                        right, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return mx_with_dtype(dtype, [&](auto t) {
+        return mxr_apply_impl<decltype(t)>(mine, from_left, from_right, compressed_bytes, num_elem, tensor, weight,
+                                           left, right, static_cast<hipStream_t>(stream));
+    });
 }
 
 int bagua_ring_one_rank_mxfp4(int dtype, void* tensor, void* weight, void* left, void* right, int num_elem,
                               bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32: return mxr_one_rank_impl<F32>(tensor, weight, left, right, num_elem, s);
-        case BAGUA_DTYPE_F16: return mxr_one_rank_impl<F16>(tensor, weight, left, right, num_elem, s);
-        case BAGUA_DTYPE_BF16: return mxr_one_rank_impl<BF16>(tensor, weight, left, right, num_elem, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return mx_with_dtype(dtype, [&](auto t) {
+        return mxr_one_rank_impl<decltype(t)>(tensor, weight, left, right, num_elem, static_cast<hipStream_t>(stream));
+    });
 }
 
 }  // extern "C"
