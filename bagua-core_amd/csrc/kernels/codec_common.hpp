@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "bagua_kernels.h"
 
 namespace bagua {
@@ -354,5 +356,49 @@ __device__ __forceinline__ QParams read_header(const uint8_t* seg) {
 }
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & (kWave - 1)); }
+
+// ------------------------------------------- host: run-time value -> template argument --
+// f(T{}) for the dtype's T; f returns the entry's status (`other`: every non-float dtype)
+template <typename F>
+static inline int with_dtype(int dtype, F&& f, int other = BAGUA_ERR_UNSUPPORTED) {
+    switch (dtype) {
+        case BAGUA_DTYPE_F32: return f(F32{});
+        case BAGUA_DTYPE_F16: return f(F16{});
+        case BAGUA_DTYPE_BF16: return f(BF16{});
+    }
+    return other;
+}
+
+// f(std::true_type / false_type{}): a launch-time choice as a template argument
+template <typename F>
+static inline void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// v is one of Vs: f(that V as a constant) and true; otherwise nothing is called and false.
+//   if (!with_one_of<1, 2, 4>(u, [&](auto U) { launch(kernel<decltype(U)::value>, ...); })) ...default...
+template <int... Vs, typename F>
+static inline bool with_one_of(int v, F&& f) {
+    bool hit = false;
+    auto try_one = [&](auto c) {
+        if (v == decltype(c)::value) {
+            f(c);
+            hit = true;
+        }
+    };
+    (try_one(std::integral_constant<int, Vs>{}), ...);
+    return hit;
+}
+
+// f(BY as a constant) for p segments, p <= kMaxFusedChunks (reduce.hip's launch table)
+template <typename F>
+static inline void with_by(int p, F&& f) {
+    switch (reduce_by(p)) {
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
 
 }  // namespace bagua

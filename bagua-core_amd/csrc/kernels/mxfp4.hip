@@ -350,8 +350,8 @@ __global__ __launch_bounds__(kBlock) void mxfp4_reduce_encode_ef_kernel(const ui
 // ------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------
-// mx_hw(), mx_grid(), the dispatch helpers (mx_with_dtype / _bool / _by) and the shared
-// argument checks: mxfp4_device.hpp
+// mx_hw(), mx_grid() and the shared argument checks: mxfp4_device.hpp; the dispatch
+// helpers (with_dtype / _bool / _by): codec_common.hpp
 
 // A block range [bb, be) of a chunk of cs elements as the range entries take it: bb a
 // multiple of the granule in [0, nb], be in [bb, nb] and either nb or a multiple of it.
@@ -408,8 +408,8 @@ static int mx_decompress_impl(const uint8_t* in, size_t in_bytes, int cs, int p,
     const int64_t last = std::min(((int64_t)cs + N - 1) / N, (int64_t)be * (kMxBlock / N));
     const int64_t nvec = last - (int64_t)bb * (kMxBlock / N);  // the range's 16-B output vectors
     const dim3 grid(mx_grid(nvec, kBlock * kMxDecodeVecs, p, "BAGUA_TUNE_MX_DECODE_BLOCKS"), p);
-    mx_with_bool(mx_hw(), [&](auto hw) {
-        mx_with_bool(nt, [&](auto nts) {
+    with_bool(mx_hw(), [&](auto hw) {
+        with_bool(nt, [&](auto nts) {
             launch(mxfp4_decode_kernel<T, decltype(hw)::value, decltype(nts)::value>, grid, dim3(kBlock), 0, s, in,
                    (int64_t)cs, static_cast<S*>(out), (int64_t)bb, (int64_t)be);
         });
@@ -440,8 +440,8 @@ static int mx_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, int
     uint8_t* seg = out + (size_t)target * (size_t)mx_segment_bytes(cs);
     const int blocks = mx_grid(be - bb, kBlock, 1, "BAGUA_TUNE_MX_MIDDLE_BLOCKS");
     const uint32_t jc = key ? (uint32_t)((int64_t)target * cs) : 0u;  // index of the own chunk's first element
-    mx_with_by(p, [&](auto by) {
-        mx_with_bool(mx_hw(), [&](auto hw) {
+    with_by(p, [&](auto by) {
+        with_bool(mx_hw(), [&](auto hw) {
             constexpr int BY = decltype(by)::value;
             constexpr bool HW = decltype(hw)::value;
             auto go = [&](auto kern) {
@@ -479,8 +479,8 @@ static int mx_compress_ef_impl(const void* input, int in_num_elem, int cs, int p
     // BAGUA_MX_EF_RESIDUAL_NT=1 / 0 forces either (A/B).
     const int env = tune_int("BAGUA_MX_EF_RESIDUAL_NT", -1);
     const bool nt = env >= 0 ? env != 0 : (int64_t)cs * p * (4 + (int64_t)sizeof(S)) > ((int64_t)256 << 20);
-    mx_with_bool(mx_hw(), [&](auto hw) {
-        mx_with_bool(nt, [&](auto ntr) {
+    with_bool(mx_hw(), [&](auto hw) {
+        with_bool(nt, [&](auto ntr) {
             launch(mxfp4_encode_ef_kernel<T, decltype(hw)::value, decltype(ntr)::value>, grid, dim3(kBlock), 0, s,
                    static_cast<const S*>(input), (int64_t)cs, residual, out);
         });
@@ -496,8 +496,8 @@ static int mx_reduce_requantize_ef_impl(const uint8_t* recv, size_t recv_bytes, 
     if (cs == 0) return BAGUA_OK;
     uint8_t* seg = out + (size_t)target * (size_t)mx_segment_bytes(cs);
     const int blocks = mx_grid(mx_blocks(cs), kBlock, 1, "BAGUA_TUNE_MX_MIDDLE_BLOCKS");
-    mx_with_by(p, [&](auto by) {
-        mx_with_bool(mx_hw(), [&](auto hw) {
+    with_by(p, [&](auto by) {
+        with_bool(mx_hw(), [&](auto hw) {
             launch(mxfp4_reduce_encode_ef_kernel<T, decltype(by)::value, decltype(hw)::value>, dim3(blocks),
                    dim3(kBlock), 0, s, recv, (int64_t)cs, p, average, residual, seg);
         });
@@ -521,7 +521,7 @@ int bagua_mxfp4_ef_state_bytes(int chunk_size, int num_chunks, size_t* worker_by
 int bagua_mxfp4_compress_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
                             uint8_t* output, size_t output_bytes, int target_chunk, float* residual,
                             bagua_stream_t stream) {
-    return mx_with_dtype(dtype, [&](auto t) {
+    return with_dtype(dtype, [&](auto t) {
         return mx_compress_ef_impl<decltype(t)>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
                                                 target_chunk, residual, static_cast<hipStream_t>(stream));
     });
@@ -530,7 +530,7 @@ int bagua_mxfp4_compress_ef(int dtype, const void* input, int input_num_element,
 int bagua_mxfp4_reduce_requantize_ef(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
                                      int num_chunks, int average, uint8_t* output, size_t output_bytes,
                                      int target_chunk, float* residual, bagua_stream_t stream) {
-    return mx_with_dtype(dtype, [&](auto t) {
+    return with_dtype(dtype, [&](auto t) {
         return mx_reduce_requantize_ef_impl<decltype(t)>(input, input_bytes, chunk_size, num_chunks, average, output,
                                                          output_bytes, target_chunk, residual,
                                                          static_cast<hipStream_t>(stream));
@@ -546,7 +546,7 @@ size_t bagua_mxfp4_compressed_bytes(int chunk_size, int num_chunks) {
 static int mx_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
                        uint8_t* output, size_t output_bytes, int target_chunk, int bb, int be, const uint64_t* key,
                        hipStream_t s) {
-    return mx_with_dtype(dtype, [&](auto t) {
+    return with_dtype(dtype, [&](auto t) {
         return mx_compress_impl<decltype(t)>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
                                              target_chunk, bb, be, key, s);
     });
@@ -554,7 +554,7 @@ static int mx_compress(int dtype, const void* input, int input_num_element, int 
 
 static int mx_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
                          void* output, int bb, int be, hipStream_t s) {
-    return mx_with_dtype(dtype, [&](auto t) {
+    return with_dtype(dtype, [&](auto t) {
         return mx_decompress_impl<decltype(t)>(input, input_bytes, chunk_size, num_chunks, output, bb, be, s);
     });
 }
@@ -562,7 +562,7 @@ static int mx_decompress(int dtype, const uint8_t* input, size_t input_bytes, in
 static int mx_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
                                 void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
                                 int bb, int be, const uint64_t* key, hipStream_t s) {
-    return mx_with_dtype(dtype, [&](auto t) {
+    return with_dtype(dtype, [&](auto t) {
         return mx_reduce_requantize_impl<decltype(t)>(input, input_bytes, chunk_size, num_chunks, tensor, average,
                                                       output, output_bytes, target_chunk, bb, be, key, s);
     });

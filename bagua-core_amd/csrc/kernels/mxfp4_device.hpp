@@ -6,8 +6,8 @@
 //           mx_load_tile / mx_store_row                       a wave tile of one tensor, f32 state back
 //           mx_reduce_block    decode and tree-sum of one block of p received segments
 //           mx_add_residual    a whole block's f32 residual onto its values
-//   host    mx_with_dtype / mx_with_bool / mx_with_by: run-time value -> template argument;
-//           the argument checks of the entries; the two launch knobs
+//   host    the argument checks of the entries; the two launch knobs (run-time value ->
+//           template argument: with_dtype / with_bool / with_by, codec_common.hpp)
 // Arithmetic of one block: mxfp4_common.hpp.
 #pragma once
 
@@ -272,33 +272,7 @@ __device__ __forceinline__ void mx_reduce_block(const uint8_t* in, int64_t segb,
 // ------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------
-// f(T{}) for the dtype's T; f returns the entry's status
-template <typename F>
-static inline int mx_with_dtype(int dtype, F&& f) {
-    switch (dtype) {
-        case BAGUA_DTYPE_F32: return f(F32{});
-        case BAGUA_DTYPE_F16: return f(F16{});
-        case BAGUA_DTYPE_BF16: return f(BF16{});
-    }
-    return BAGUA_ERR_UNSUPPORTED;
-}
-
-// f(std::true_type / false_type{}): a launch-time choice as a template argument
-template <typename F>
-static inline void mx_with_bool(bool b, F&& f) {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
-
-// f(BY as a constant) for p segments, p <= kMaxFusedChunks (reduce.hip's launch table)
-template <typename F>
-static inline void mx_with_by(int p, F&& f) {
-    switch (reduce_by(p)) {
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        default: f(std::integral_constant<int, 8>{}); break;
-    }
-}
+// run-time value -> template argument: with_dtype / with_bool / with_by, codec_common.hpp
 
 // the argument checks the entries share: p chunks of cs elements (the encode and the decode
 // put chunks on grid.y: max_p = kMxGridChunks), ...

@@ -314,7 +314,7 @@ static int mxr_mix_impl(const void* t, const void* l, const void* r, const void*
     if (!mxr_aligned16(t, l, r, w)) return BAGUA_ERR_UNSUPPORTED;
     const float f13 = mx_ring_factor(T::kDtype, 1.0 / 3.0), f53 = mx_ring_factor(T::kDtype, -5.0 / 3.0);
     const dim3 grid(mxr_tile_grid<T>(n, "BAGUA_TUNE_MX_RING_MIX_BLOCKS"));
-    mx_with_bool(mx_hw(), [&](auto hw) {
+    with_bool(mx_hw(), [&](auto hw) {
         launch(mxfp4_ring_mix_kernel<T, decltype(hw)::value>, grid, dim3(kBlock), 0, s, static_cast<const S*>(t),
                static_cast<const S*>(l), static_cast<const S*>(r), static_cast<const S*>(w), (int64_t)n, f13, f53, out);
     });
@@ -328,8 +328,8 @@ static int mxr_one_rank_impl(void* t, void* w, void* l, void* r, int n, hipStrea
     if (!mxr_aligned16(t, w, l, r)) return BAGUA_ERR_UNSUPPORTED;
     const float f13 = mx_ring_factor(T::kDtype, 1.0 / 3.0), f53 = mx_ring_factor(T::kDtype, -5.0 / 3.0);
     const dim3 grid(mxr_tile_grid<T>(n, "BAGUA_TUNE_MX_RING_ONE_RANK_BLOCKS"));
-    mx_with_bool(mx_hw(), [&](auto hw) {
-        mx_with_bool(mxr_nt_stores<T>(n), [&](auto nts) {
+    with_bool(mx_hw(), [&](auto hw) {
+        with_bool(mxr_nt_stores<T>(n), [&](auto nts) {
             launch(mxfp4_ring_one_rank_kernel<T, decltype(hw)::value, decltype(nts)::value>, grid, dim3(kBlock), 0, s,
                    static_cast<S*>(t), static_cast<S*>(w), static_cast<S*>(l), static_cast<S*>(r), (int64_t)n, f13, f53);
         });
@@ -347,8 +347,8 @@ static int mxr_apply_impl(const uint8_t* mine, const uint8_t* from_left, const u
     if (!mxr_aligned16(t, w, l, r)) return BAGUA_ERR_UNSUPPORTED;
     const int64_t nvec = ((int64_t)n + Vec<T>::N - 1) / Vec<T>::N;
     const dim3 grid(mx_grid(nvec, kBlock * kMxRingApplyVecs, 1, "BAGUA_TUNE_MX_RING_APPLY_BLOCKS"));
-    mx_with_bool(mx_hw(), [&](auto hw) {
-        mx_with_bool(mxr_nt_stores<T>(n), [&](auto nts) {
+    with_bool(mx_hw(), [&](auto hw) {
+        with_bool(mxr_nt_stores<T>(n), [&](auto nts) {
             launch(mxfp4_ring_apply_kernel<T, decltype(hw)::value, decltype(nts)::value>, grid, dim3(kBlock), 0, s, mine,
                    from_left, from_right, (int64_t)n, static_cast<S*>(t), static_cast<S*>(w), static_cast<S*>(l),
                    static_cast<S*>(r));
@@ -365,7 +365,7 @@ extern "C" {
 
 int bagua_ring_mix_mxfp4(int dtype, const void* tensor, const void* left, const void* right, const void* weight,
                          int num_elem, uint8_t* output, size_t output_bytes, bagua_stream_t stream) {
-    return mx_with_dtype(dtype, [&](auto t) {
+    return with_dtype(dtype, [&](auto t) {
         return mxr_mix_impl<decltype(t)>(tensor, left, right, weight, num_elem, output, output_bytes,
                                          static_cast<hipStream_t>(stream));
     });
@@ -374,7 +374,7 @@ int bagua_ring_mix_mxfp4(int dtype, const void* tensor, const void* left, const 
 int bagua_ring_apply_mxfp4(int dtype, const uint8_t* mine, const uint8_t* from_left, const uint8_t* from_right,
                            size_t compressed_bytes, int num_elem, void* tensor, void* weight, void* left, void* right,
                            bagua_stream_t stream) {
-    return mx_with_dtype(dtype, [&](auto t) {
+    return with_dtype(dtype, [&](auto t) {
         return mxr_apply_impl<decltype(t)>(mine, from_left, from_right, compressed_bytes, num_elem, tensor, weight,
                                            left, right, static_cast<hipStream_t>(stream));
     });
@@ -382,7 +382,7 @@ int bagua_ring_apply_mxfp4(int dtype, const uint8_t* mine, const uint8_t* from_l
 
 int bagua_ring_one_rank_mxfp4(int dtype, void* tensor, void* weight, void* left, void* right, int num_elem,
                               bagua_stream_t stream) {
-    return mx_with_dtype(dtype, [&](auto t) {
+    return with_dtype(dtype, [&](auto t) {
         return mxr_one_rank_impl<decltype(t)>(tensor, weight, left, right, num_elem, static_cast<hipStream_t>(stream));
     });
 }

@@ -72,22 +72,7 @@ __global__ __launch_bounds__(kBlock) void onebit_encode_kernel(
         for (int u = 0; u < TPI; ++u) {
             const int64_t t = t0 + u;
             if (t >= t_end) break;
-            // the lane's 16 sign bits form its own 16-bit field (bit sub*4+e)
-            uint32_t field = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) field |= (a[u][k][e] < 0.0f ? 1u : 0u) << (k * 4 + e);
-            // even lanes store their field and the odd neighbour's as one dword
-            const uint32_t next = odd_neighbour(field);
-            if ((lane & 1) == 0) reinterpret_cast<uint32_t*>(bits + t * kObTileBytes)[lane >> 1] = field | (next << 16);
-            float ab[4][4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ab[k][e] = __builtin_fabsf(a[u][k][e]);
-            const float s = wave_tree_sum_lane0(lane_tree(ab));
-            if (lane == 0) part[t] = s;
+            ob_emit_tile(a[u], bits, part, t, lane);
         }
     }
 }
@@ -99,26 +84,7 @@ __global__ __launch_bounds__(kObFinalizeThreads) void onebit_finalize_kernel(
     const float* __restrict__ partials, int64_t tiles_per_chunk, int64_t in_num_elem, int64_t cs, int target,
     uint8_t* __restrict__ out, int64_t chunk_offset, int64_t out_bytes, int num_chunks) {
     __shared__ float lvl[2][2048];  // level >= 2 values: <= ceil(2^21 / 1024)
-    const int c = target < 0 ? (int)blockIdx.x : target;
-    const int64_t n = ob_valid(in_num_elem, cs, c);
-    const float* part = partials + (int64_t)blockIdx.x * tiles_per_chunk;
-    const int64_t m1 = (n + kObTile - 1) / kObTile;  // tiles holding valid elements
-    const float total = chunk_tree([part](int64_t r) { return part[r]; }, m1, lvl);
-    uint8_t* seg = out + (int64_t)c * chunk_offset;
-    if (threadIdx.x < 32) {
-        const float scale = n > 0 ? total / (float)n : 0.0f;
-        const uint32_t sb = __float_as_uint(scale), nb = (uint32_t)n;
-        const int t = threadIdx.x;
-        uint32_t b = 0;
-        if (t < 4) b = (sb >> (8 * t)) & 0xff;
-        else if (t < 8) b = (nb >> (8 * (t - 4))) & 0xff;
-        seg[t] = (uint8_t)b;
-    }
-    const int64_t tiles = (cs + kObTile - 1) / kObTile;
-    for (int64_t j = 32 + tiles * kObTileBytes + threadIdx.x; j < chunk_offset; j += kObFinalizeThreads) seg[j] = 0;
-    if (target < 0 && c == num_chunks - 1)
-        for (int64_t j = (int64_t)num_chunks * chunk_offset + threadIdx.x; j < out_bytes; j += kObFinalizeThreads)
-            out[j] = 0;
+    ob_finalize(partials, tiles_per_chunk, in_num_elem, cs, target, out, chunk_offset, out_bytes, num_chunks, lvl);
 }
 
 // ------------------------------------------------------------------------
@@ -143,14 +109,7 @@ __global__ __launch_bounds__(kBlock) void onebit_decode_kernel(const uint8_t* __
     for (int64_t t = t_begin + wave; t < t_end; t += nwaves) {
         // the lane's own 16-bit field: no cross-lane traffic
         const uint32_t field = reinterpret_cast<const uint16_t*>(bits + t * kObTileBytes)[lane];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float f[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)  // bit ? -scale : +scale, as a sign-bit flip
-                f[e] = __uint_as_float(sbits ^ ((field << (31 - (k * 4 + e))) & 0x80000000u));
-            store4<T, NTS>(dst, t * kObTile + k * 256 + lane * 4, cs, vec, f);
-        }
+        ob_decode_field<T, NTS>(field, sbits, dst, t, cs, vec, lane);
     }
 }
 
@@ -169,12 +128,7 @@ __global__ __launch_bounds__(kBlock) void onebit_reduce_encode_kernel(
     const uint8_t* __restrict__ in, int64_t chunk_offset, int64_t cs, int p, typename T::storage* __restrict__ chunk,
     uint8_t* __restrict__ out_seg, float* __restrict__ part) {
     __shared__ float pos[kMaxFusedChunks], neg[kMaxFusedChunks];
-    if (threadIdx.x < (unsigned)p) {  // segment c decodes to +-scale_c as stored in T
-        float sc;
-        __builtin_memcpy(&sc, in + (int64_t)threadIdx.x * chunk_offset, 4);
-        pos[threadIdx.x] = as_stored<T>(sc);
-        neg[threadIdx.x] = as_stored<T>(-sc);
-    }
+    ob_scale_tables<T>(in, chunk_offset, p, pos, neg);
     __syncthreads();
     using S = typename T::storage;
     const int lane = lane_id();
@@ -185,6 +139,9 @@ __global__ __launch_bounds__(kBlock) void onebit_reduce_encode_kernel(
     const float pf = (float)p;
     uint8_t* bits = out_seg + 32;
     for (int64_t t = wave; t < tiles; t += nwaves) {
+        // the BY-wide accumulation, written out here and in onebit_reduce_encode_ef_kernel
+        // (onebit_ef.hip; keep the two in step): as a shared step it cost several
+        // instantiations an occupancy step
         float s[16][BY];
 #pragma unroll
         for (int b = 0; b < 16; ++b)
@@ -223,15 +180,7 @@ __global__ __launch_bounds__(kBlock) void onebit_reduce_encode_kernel(
 #pragma unroll
             for (int k = 0; k < 4; ++k) store4<T>(chunk, t * kObTile + k * 256 + lane * 4, cs, vec, x[k]);
         }
-        const uint32_t next = odd_neighbour(field);
-        if ((lane & 1) == 0) reinterpret_cast<uint32_t*>(bits + t * kObTileBytes)[lane >> 1] = field | (next << 16);
-        float ab[4][4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ab[k][e] = __builtin_fabsf(x[k][e]);
-        const float sum = wave_tree_sum_lane0(lane_tree(ab));
-        if (lane == 0) part[t] = sum;
+        ob_emit_tile(x, field, bits, part, t, lane);
     }
 }
 
@@ -321,12 +270,7 @@ __global__ __launch_bounds__(kBlock) void onebit_reduce_encode_lut_kernel(
     constexpr bool WIDE = PMAX > 8;
     __shared__ float pos[kMaxFusedChunks], neg[kMaxFusedChunks];
     __shared__ float lut[WIDE ? 2 : 1][256];
-    if (threadIdx.x < (unsigned)p) {  // segment c decodes to +-scale_c as stored in T
-        float sc;
-        __builtin_memcpy(&sc, in + (int64_t)threadIdx.x * chunk_offset, 4);
-        pos[threadIdx.x] = as_stored<T>(sc);
-        neg[threadIdx.x] = as_stored<T>(-sc);
-    }
+    ob_scale_tables<T>(in, chunk_offset, p, pos, neg);
     __syncthreads();
     const float pf = (float)p;
     for (int i = threadIdx.x; i < 256; i += kBlock) {
@@ -402,11 +346,7 @@ __global__ __launch_bounds__(kBlock) void onebit_reduce_encode_lut_kernel(
                 float q[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) q[k] = gtab[((f0 >> (4 * k)) & 15u) | (((f1 >> (4 * k)) & 15u) << 4)];
-                const uint32_t next = odd_neighbour(field);
-                if ((lane & 1) == 0)
-                    reinterpret_cast<uint32_t*>(bits + t * kObTileBytes)[lane >> 1] = field | (next << 16);
-                const float sum = wave_tree_sum_lane0((q[0] + q[1]) + (q[2] + q[3]));
-                if (lane == 0) part[t] = sum;
+                ob_emit_field(field, (q[0] + q[1]) + (q[2] + q[3]), bits, part, t, lane);
                 return;
             }
         }
@@ -430,11 +370,7 @@ __global__ __launch_bounds__(kBlock) void onebit_reduce_encode_lut_kernel(
                     q[k] = __uint_as_float(a.x) + __uint_as_float(b.x);
                     field |= (a.y | (b.y << 2)) << (4 * k);
                 }
-                const uint32_t next = odd_neighbour(field);
-                if ((lane & 1) == 0)
-                    reinterpret_cast<uint32_t*>(bits + t * kObTileBytes)[lane >> 1] = field | (next << 16);
-                const float sum = wave_tree_sum_lane0((q[0] + q[1]) + (q[2] + q[3]));
-                if (lane == 0) part[t] = sum;
+                ob_emit_field(field, (q[0] + q[1]) + (q[2] + q[3]), bits, part, t, lane);
                 return;
             }
         }
@@ -478,15 +414,7 @@ __global__ __launch_bounds__(kBlock) void onebit_reduce_encode_lut_kernel(
 #pragma unroll
             for (int k = 0; k < 4; ++k) store4<T>(chunk, t * kObTile + k * 256 + lane * 4, cs, vec, x[k]);
         }
-        const uint32_t next = odd_neighbour(field);
-        if ((lane & 1) == 0) reinterpret_cast<uint32_t*>(bits + t * kObTileBytes)[lane >> 1] = field | (next << 16);
-        float ab[4][4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ab[k][e] = __builtin_fabsf(x[k][e]);
-        const float sum = wave_tree_sum_lane0(lane_tree(ab));
-        if (lane == 0) part[t] = sum;
+        ob_emit_tile(x, field, bits, part, t, lane);
     };
     // U tiles per wave iteration, all their loads issued before the first is used: at
     // p <= 2 a tile's input is 4 B per lane, and one tile at a time kept a wave waiting a
@@ -624,15 +552,7 @@ __global__ __launch_bounds__(kBlock) void onebit_one_rank_decode_kernel(const ui
     const uint32_t sbits = __float_as_uint(o->scale2), mpos = o->mpos, mneg = o->mneg;
     for (int64_t t = wave; t < tiles; t += nwaves) {
         const uint32_t f1 = reinterpret_cast<const uint16_t*>(bits + t * kObTileBytes)[lane];
-        const uint32_t field = (f1 & mneg) | (~f1 & mpos);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float f[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)  // bit ? -scale2 : +scale2, as a sign-bit flip
-                f[e] = __uint_as_float(sbits ^ ((field << (31 - (k * 4 + e))) & 0x80000000u));
-            store4<T, NTS>(out, t * kObTile + k * 256 + lane * 4, cs, vec, f);
-        }
+        ob_decode_field<T, NTS>((f1 & mneg) | (~f1 & mpos), sbits, out, t, cs, vec, lane);  // +-scale2
     }
 }
 
@@ -652,24 +572,21 @@ static int ob_compress_impl(const void* input, int in_num_elem, int cs, int p, u
         return BAGUA_ERR_INVALID_ARG;
     const int64_t co = (int64_t)(out_bytes / (size_t)p);
     const int64_t tiles = ob_tiles(cs);
-    if (co < 32 + tiles * kObTileBytes) return BAGUA_ERR_INVALID_ARG;
     const int nact = target < 0 ? p : 1;
-    if (!ws || ws_bytes < (size_t)nact * (size_t)(tiles > 0 ? tiles : 1) * sizeof(float)) return BAGUA_ERR_WORKSPACE;
-    if (((uintptr_t)out + 32) % 4 || co % 4) return BAGUA_ERR_INVALID_ARG;  // bit tiles are written as dwords
+    if (const int e = ob_check_encode(out, co, tiles, ws, ws_bytes, nact)) return e;
     float* partials = static_cast<float*>(ws);
     const int64_t tb = stage == 2 ? 0 : t_begin, te = stage == 2 ? tiles : (t_end < tiles ? t_end : tiles);
     // nt loads: default-policy loads behind the decode's default-policy stores take
     // 77 us instead of 47 (profiles/r01_decode_store_ab.jsonl)
     if (stage != 2 && te > tb) {
         const dim3 grid(ob_blocks(te - tb, nact, tune_int("BAGUA_TUNE_OB_ENCODE_BLOCKS", kObEncodeBlocks)), nact);
+        auto go = [&](auto kern) {
+            launch(kern, grid, dim3(kBlock), 0, s, static_cast<const S*>(input), (int64_t)in_num_elem, (int64_t)cs,
+                   target, out, co, partials, tiles, tb, te);
+        };
         // BAGUA_TUNE_OB_ENCODE_TPI=2: f32 tiles two per wave iteration (A/B; 16-bit types always take two)
-        if (sizeof(S) == 4 && tune_int("BAGUA_TUNE_OB_ENCODE_TPI", 1) == 2)
-            launch(onebit_encode_kernel<T, 2, true>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
-                   (int64_t)in_num_elem, (int64_t)cs, target, out, co, partials, tiles, tb, te);
-        else
-            launch(onebit_encode_kernel<T, sizeof(S) == 4 ? 1 : 2, true>, grid, dim3(kBlock), 0, s,
-                   static_cast<const S*>(input), (int64_t)in_num_elem, (int64_t)cs, target, out, co, partials, tiles,
-                   tb, te);
+        if (sizeof(S) == 4 && tune_int("BAGUA_TUNE_OB_ENCODE_TPI", 1) == 2) go(onebit_encode_kernel<T, 2, true>);
+        else go(onebit_encode_kernel<T, sizeof(S) == 4 ? 1 : 2, true>);
     }
     if (stage != 1)
         launch(onebit_finalize_kernel, dim3(nact), dim3(kObFinalizeThreads), 0, s, partials, tiles,
@@ -684,72 +601,38 @@ static int ob_decompress_impl(const uint8_t* in, size_t in_bytes, int cs, int p,
     if (p <= 0 || p > 65535 || cs < 0 || !in || !out || t_begin < 0 || t_end < t_begin) return BAGUA_ERR_INVALID_ARG;
     const int64_t co = (int64_t)(in_bytes / (size_t)p);
     const int64_t tiles = ob_tiles(cs);
-    if (co < 32 + tiles * kObTileBytes) return BAGUA_ERR_INVALID_ARG;
-    if (((uintptr_t)in + 32) % 4 || co % 4) return BAGUA_ERR_INVALID_ARG;
+    if (!ob_holds(co, tiles) || !ob_aligned(in, co)) return BAGUA_ERR_INVALID_ARG;
     const int64_t te = t_end < tiles ? t_end : tiles;
     if (te <= t_begin) return BAGUA_OK;
-    // Store policy by the bucket's size (all p chunks, not this launch's tile range):
-    // up to the 256 MiB Infinity Cache, default-policy stores (256 MiB f32: decode 42.6
-    // vs 47.8 us with nt stores, and the next encode unaffected,
-    // profiles/r04_onebit_decode_store_ab.jsonl); past it the cache cannot keep the
-    // dirty lines, which the next encode then writes back (1 GiB: encode 196 -> 186 us,
-    // decode 201 -> 194 us with nt stores, same file).  BAGUA_OB_DECODE_NT=1 / 0
-    // forces either (A/B).
-    const int env = tune_int("BAGUA_OB_DECODE_NT", -1);
-    const int nt = env >= 0 ? env : ((int64_t)cs * p * (int64_t)sizeof(S) > ((int64_t)256 << 20) ? 1 : 0);
+    // Store policy by the bucket's size (all p chunks, not this launch's tile range),
+    // ob_nt_by_size: up to 256 MiB default-policy stores (256 MiB f32: decode 42.6 vs
+    // 47.8 us with nt stores, and the next encode unaffected,
+    // profiles/r04_onebit_decode_store_ab.jsonl); past it nt stores (1 GiB: encode
+    // 196 -> 186 us, decode 201 -> 194 us, same file)
+    const bool nt = ob_nt_by_size((int64_t)cs * p * (int64_t)sizeof(S), "BAGUA_OB_DECODE_NT");
     const dim3 grid(ob_blocks(te - t_begin, p, tune_int("BAGUA_TUNE_OB_DECODE_BLOCKS", kObDecodeBlocks)), p);
-    if (nt == 1)
-        launch(onebit_decode_kernel<T, true>, grid, dim3(kBlock), 0, s, in, co, (int64_t)cs, static_cast<S*>(out),
-               t_begin, te);
-    else
-        launch(onebit_decode_kernel<T, false>, grid, dim3(kBlock), 0, s, in, co, (int64_t)cs, static_cast<S*>(out),
-               t_begin, te);
+    with_bool(nt, [&](auto nts) {
+        launch(onebit_decode_kernel<T, decltype(nts)::value>, grid, dim3(kBlock), 0, s, in, co, (int64_t)cs,
+               static_cast<S*>(out), t_begin, te);
+    });
     return check_launch();
-}
-
-template <typename T, int BY, bool AVG>
-static void launch_ob_reduce(const uint8_t* in, int64_t co, int64_t cs, int p, typename T::storage* chunk,
-                             uint8_t* seg, float* part, int blocks, hipStream_t s) {
-    if (chunk)
-        launch(onebit_reduce_encode_kernel<T, BY, AVG, true>, dim3(blocks), dim3(kBlock), 0, s, in, co, cs, p, chunk,
-               seg, part);
-    else
-        launch(onebit_reduce_encode_kernel<T, BY, AVG, false>, dim3(blocks), dim3(kBlock), 0, s, in, co, cs, p,
-               chunk, seg, part);
 }
 
 template <typename T, int PMAX>
 static void launch_ob_reduce_lut(const uint8_t* in, int64_t co, int64_t cs, int p, int average,
                                  typename T::storage* chunk, uint8_t* seg, float* part, int blocks, hipStream_t s) {
+    auto go = [&](auto kern) {
+        launch(kern, dim3(blocks), dim3(kBlock), 0, s, in, co, cs, p, average, chunk, seg, part);
+    };
     if constexpr (PMAX <= 4) {  // tiles per wave iteration of the re-encode: BAGUA_OB_MIDDLE_U (A/B)
         const int u = tune_int("BAGUA_OB_MIDDLE_U", PMAX == 2 ? 2 : 1);
-        if (!chunk && u == 1) {
-            launch(onebit_reduce_encode_lut_kernel<T, PMAX, false, 1>, dim3(blocks), dim3(kBlock), 0, s, in, co, cs,
-                   p, average, chunk, seg, part);
+        if (!chunk && with_one_of<1, 2, 4, 8>(u, [&](auto ut) {
+                go(onebit_reduce_encode_lut_kernel<T, PMAX, false, decltype(ut)::value>);
+            }))
             return;
-        }
-        if (!chunk && u == 2) {
-            launch(onebit_reduce_encode_lut_kernel<T, PMAX, false, 2>, dim3(blocks), dim3(kBlock), 0, s, in, co, cs,
-                   p, average, chunk, seg, part);
-            return;
-        }
-        if (!chunk && u == 4) {
-            launch(onebit_reduce_encode_lut_kernel<T, PMAX, false, 4>, dim3(blocks), dim3(kBlock), 0, s, in, co, cs,
-                   p, average, chunk, seg, part);
-            return;
-        }
-        if (!chunk && u == 8) {
-            launch(onebit_reduce_encode_lut_kernel<T, PMAX, false, 8>, dim3(blocks), dim3(kBlock), 0, s, in, co, cs,
-                   p, average, chunk, seg, part);
-            return;
-        }
     }
-    if (chunk)
-        launch(onebit_reduce_encode_lut_kernel<T, PMAX, true>, dim3(blocks), dim3(kBlock), 0, s, in, co, cs, p,
-               average, chunk, seg, part);
-    else
-        launch(onebit_reduce_encode_lut_kernel<T, PMAX, false>, dim3(blocks), dim3(kBlock), 0, s, in, co, cs, p,
-               average, chunk, seg, part);
+    if (chunk) go(onebit_reduce_encode_lut_kernel<T, PMAX, true>);
+    else go(onebit_reduce_encode_lut_kernel<T, PMAX, false>);
 }
 
 template <typename T>
@@ -757,13 +640,9 @@ static int ob_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, int
                                      int average, uint8_t* out, size_t out_bytes, int target, void* ws,
                                      size_t ws_bytes, hipStream_t s) {
     using S = typename T::storage;
-    if (p <= 0 || p > kMaxFusedChunks || cs < 0 || target < 0 || target >= p || !recv || !out)
-        return BAGUA_ERR_UNSUPPORTED;  // caller runs decompress + reduce + compress
+    if (const int e = ob_check_middle(recv, recv_bytes, cs, p, out, out_bytes, target, ws, ws_bytes)) return e;
     const int64_t co_in = (int64_t)(recv_bytes / (size_t)p), co = (int64_t)(out_bytes / (size_t)p);
     const int64_t tiles = ob_tiles(cs);
-    if (co_in < 32 + tiles * kObTileBytes || co < 32 + tiles * kObTileBytes) return BAGUA_ERR_INVALID_ARG;
-    if (((uintptr_t)recv + 32) % 4 || co_in % 4 || ((uintptr_t)out + 32) % 4 || co % 4) return BAGUA_ERR_INVALID_ARG;
-    if (!ws || ws_bytes < (size_t)(tiles > 0 ? tiles : 1) * sizeof(float)) return BAGUA_ERR_WORKSPACE;
     S* chunk = tensor ? static_cast<S*>(tensor) + (int64_t)target * cs : nullptr;  // nullptr: not stored
     float* part = static_cast<float*>(ws);
     uint8_t* seg = out + (int64_t)target * co;
@@ -785,20 +664,15 @@ static int ob_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, int
             launch_ob_reduce_lut<T, 16>(recv, co_in, cs, p, average, chunk, seg, part, blocks, s);
     } else if (tiles > 0) {
         const int blocks = ob_blocks(tiles, 1);
-        switch (reduce_by(p)) {
-            case 2:
-                if (average) launch_ob_reduce<T, 2, true>(recv, co_in, cs, p, chunk, seg, part, blocks, s);
-                else launch_ob_reduce<T, 2, false>(recv, co_in, cs, p, chunk, seg, part, blocks, s);
-                break;
-            case 4:
-                if (average) launch_ob_reduce<T, 4, true>(recv, co_in, cs, p, chunk, seg, part, blocks, s);
-                else launch_ob_reduce<T, 4, false>(recv, co_in, cs, p, chunk, seg, part, blocks, s);
-                break;
-            default:
-                if (average) launch_ob_reduce<T, 8, true>(recv, co_in, cs, p, chunk, seg, part, blocks, s);
-                else launch_ob_reduce<T, 8, false>(recv, co_in, cs, p, chunk, seg, part, blocks, s);
-                break;
-        }
+        with_by(p, [&](auto by) {
+            with_bool(average != 0, [&](auto avg) {
+                with_bool(chunk != nullptr, [&](auto store) {
+                    launch(onebit_reduce_encode_kernel<T, decltype(by)::value, decltype(avg)::value,
+                                                       decltype(store)::value>,
+                           dim3(blocks), dim3(kBlock), 0, s, recv, co_in, (int64_t)cs, p, chunk, seg, part);
+                });
+            });
+        });
     }
     // header + slack of the own segment (the tensor is fully valid: num_elem = p * cs)
     launch(onebit_finalize_kernel, dim3(1), dim3(kObFinalizeThreads), 0, s, part, tiles, (int64_t)p * cs,
@@ -836,15 +710,12 @@ static int ob_one_rank_impl(void* tensor, int n, int average, void* ws, size_t w
            reinterpret_cast<OneRankOut*>(seg));
     // 3. the result, from the bits (store policy as the decode's, by size)
     if (tiles > 0) {
-        const int env = tune_int("BAGUA_OB_DECODE_NT", -1);
-        const int nt = env >= 0 ? env : ((int64_t)n * (int64_t)sizeof(S) > ((int64_t)256 << 20) ? 1 : 0);
+        const bool nt = ob_nt_by_size((int64_t)n * (int64_t)sizeof(S), "BAGUA_OB_DECODE_NT");
         const dim3 grid(ob_blocks(tiles, 1, tune_int("BAGUA_TUNE_OB_DECODE_BLOCKS", kObDecodeBlocks)));
-        if (nt == 1)
-            launch(onebit_one_rank_decode_kernel<T, true>, grid, dim3(kBlock), 0, s, seg + 32,
+        with_bool(nt, [&](auto nts) {
+            launch(onebit_one_rank_decode_kernel<T, decltype(nts)::value>, grid, dim3(kBlock), 0, s, seg + 32,
                    reinterpret_cast<const OneRankOut*>(seg), (int64_t)n, static_cast<S*>(tensor), tiles);
-        else
-            launch(onebit_one_rank_decode_kernel<T, false>, grid, dim3(kBlock), 0, s, seg + 32,
-                   reinterpret_cast<const OneRankOut*>(seg), (int64_t)n, static_cast<S*>(tensor), tiles);
+        });
     }
     return check_launch();
 }
@@ -863,13 +734,10 @@ size_t bagua_onebit_one_rank_workspace_bytes(int num_elem) {
 
 int bagua_onebit_centralized_one_rank(int dtype, void* tensor, int num_elem, int average, void* workspace,
                                       size_t workspace_bytes, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32: return ob_one_rank_impl<F32>(tensor, num_elem, average, workspace, workspace_bytes, s);
-        case BAGUA_DTYPE_F16: return ob_one_rank_impl<F16>(tensor, num_elem, average, workspace, workspace_bytes, s);
-        case BAGUA_DTYPE_BF16: return ob_one_rank_impl<BF16>(tensor, num_elem, average, workspace, workspace_bytes, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return with_dtype(dtype, [&](auto t) {
+        return ob_one_rank_impl<decltype(t)>(tensor, num_elem, average, workspace, workspace_bytes,
+                                             static_cast<hipStream_t>(stream));
+    });
 }
 
 size_t bagua_onebit_compressed_bytes(int chunk_size, int num_chunks) {
@@ -881,33 +749,35 @@ size_t bagua_onebit_workspace_bytes(int chunk_size, int num_chunks) {
     return (size_t)(num_chunks > 0 ? num_chunks : 1) * (size_t)(t > 0 ? t : 1) * sizeof(float) + 256;
 }
 
+// the whole-chunk entries are stage 0 / every tile of the range entries' code
+static int ob_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                       uint8_t* output, size_t output_bytes, void* workspace, size_t workspace_bytes, int target_chunk,
+                       bagua_stream_t stream, int stage, int64_t tile_begin, int64_t tile_end) {
+    return with_dtype(dtype, [&](auto t) {
+        return ob_compress_impl<decltype(t)>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
+                                             workspace, workspace_bytes, target_chunk,
+                                             static_cast<hipStream_t>(stream), stage, tile_begin, tile_end);
+    });
+}
+
+static int ob_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                         void* output, bagua_stream_t stream, int64_t tile_begin, int64_t tile_end) {
+    return with_dtype(dtype, [&](auto t) {
+        return ob_decompress_impl<decltype(t)>(input, input_bytes, chunk_size, num_chunks, output,
+                                               static_cast<hipStream_t>(stream), tile_begin, tile_end);
+    });
+}
+
 int bagua_onebit_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
                           uint8_t* output, size_t output_bytes, void* workspace, size_t workspace_bytes,
                           int target_chunk, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return ob_compress_impl<F32>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                         workspace, workspace_bytes, target_chunk, s);
-        case BAGUA_DTYPE_F16:
-            return ob_compress_impl<F16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                         workspace, workspace_bytes, target_chunk, s);
-        case BAGUA_DTYPE_BF16:
-            return ob_compress_impl<BF16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                          workspace, workspace_bytes, target_chunk, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return ob_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, workspace,
+                       workspace_bytes, target_chunk, stream, 0, 0, INT64_MAX);
 }
 
 int bagua_onebit_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
                             void* output, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32: return ob_decompress_impl<F32>(input, input_bytes, chunk_size, num_chunks, output, s);
-        case BAGUA_DTYPE_F16: return ob_decompress_impl<F16>(input, input_bytes, chunk_size, num_chunks, output, s);
-        case BAGUA_DTYPE_BF16: return ob_decompress_impl<BF16>(input, input_bytes, chunk_size, num_chunks, output, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return ob_decompress(dtype, input, input_bytes, chunk_size, num_chunks, output, stream, 0, INT64_MAX);
 }
 
 int bagua_onebit_piece_range(int chunk_size, int pieces, int piece, int* tile_begin, int* tile_end) {
@@ -923,19 +793,8 @@ int bagua_onebit_piece_range(int chunk_size, int pieces, int piece, int* tile_be
 int bagua_onebit_encode_range(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
                               uint8_t* output, size_t output_bytes, void* workspace, size_t workspace_bytes,
                               int tile_begin, int tile_end, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return ob_compress_impl<F32>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                         workspace, workspace_bytes, -1, s, 1, tile_begin, tile_end);
-        case BAGUA_DTYPE_F16:
-            return ob_compress_impl<F16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                         workspace, workspace_bytes, -1, s, 1, tile_begin, tile_end);
-        case BAGUA_DTYPE_BF16:
-            return ob_compress_impl<BF16>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                          workspace, workspace_bytes, -1, s, 1, tile_begin, tile_end);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return ob_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, workspace,
+                       workspace_bytes, -1, stream, 1, tile_begin, tile_end);
 }
 
 int bagua_onebit_finalize(const void* workspace, size_t workspace_bytes, int input_num_element, int chunk_size,
@@ -947,35 +806,17 @@ int bagua_onebit_finalize(const void* workspace, size_t workspace_bytes, int inp
 
 int bagua_onebit_decompress_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
                                   int num_chunks, void* output, int tile_begin, int tile_end, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return ob_decompress_impl<F32>(input, input_bytes, chunk_size, num_chunks, output, s, tile_begin, tile_end);
-        case BAGUA_DTYPE_F16:
-            return ob_decompress_impl<F16>(input, input_bytes, chunk_size, num_chunks, output, s, tile_begin, tile_end);
-        case BAGUA_DTYPE_BF16:
-            return ob_decompress_impl<BF16>(input, input_bytes, chunk_size, num_chunks, output, s, tile_begin,
-                                            tile_end);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return ob_decompress(dtype, input, input_bytes, chunk_size, num_chunks, output, stream, tile_begin, tile_end);
 }
 
 int bagua_onebit_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
                                    int num_chunks, void* tensor, int average, uint8_t* output, size_t output_bytes,
                                    int target_chunk, void* workspace, size_t workspace_bytes, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BAGUA_DTYPE_F32:
-            return ob_reduce_requantize_impl<F32>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
-                                                  output_bytes, target_chunk, workspace, workspace_bytes, s);
-        case BAGUA_DTYPE_F16:
-            return ob_reduce_requantize_impl<F16>(input, input_bytes, chunk_size, num_chunks, tensor, average, output,
-                                                  output_bytes, target_chunk, workspace, workspace_bytes, s);
-        case BAGUA_DTYPE_BF16:
-            return ob_reduce_requantize_impl<BF16>(input, input_bytes, chunk_size, num_chunks, tensor, average,
-                                                   output, output_bytes, target_chunk, workspace, workspace_bytes, s);
-    }
-    return BAGUA_ERR_UNSUPPORTED;
+    return with_dtype(dtype, [&](auto t) {
+        return ob_reduce_requantize_impl<decltype(t)>(input, input_bytes, chunk_size, num_chunks, tensor, average,
+                                                      output, output_bytes, target_chunk, workspace, workspace_bytes,
+                                                      static_cast<hipStream_t>(stream));
+    });
 }
 
 size_t onebit_temp_size_host(int chunk_size, int num_chunks) {

@@ -228,6 +228,113 @@ __device__ __forceinline__ float chunk_tree(const Get& get, int64_t m1, float (&
     return upper_tree(m1, lvl);
 }
 
+// ------------------------------------------------------------------------
+// The steps the 1-bit kernels are composed of, each stated once.  All of them are
+// inlined into the tile loops and take their arrays by reference (the loops are
+// tuned to a VGPR step: onebit_ef.hip's worker encode).
+// ------------------------------------------------------------------------
+// The two stores of a tile: even lanes store their 16-bit sign field and the odd neighbour's
+// as one dword; lane 0 stores the tile's |v| partial.  wave_tree_sum_lane0 needs every lane
+// of the wave active, so these stay outside any per-lane guard: padding past cs is zeroed
+// values, never masked lanes
+__device__ __forceinline__ void ob_store_field(uint32_t field, uint8_t* bits, int64_t t, int lane) {
+    const uint32_t next = odd_neighbour(field);
+    if ((lane & 1) == 0) reinterpret_cast<uint32_t*>(bits + t * kObTileBytes)[lane >> 1] = field | (next << 16);
+}
+__device__ __forceinline__ void ob_store_partial(float lane_sum, float* part, int64_t t, int lane) {
+    const float s = wave_tree_sum_lane0(lane_sum);
+    if (lane == 0) part[t] = s;
+}
+// tail of a tile for a lane that has its field and its part of the |v| tree already (the
+// table kernel's fast paths)
+__device__ __forceinline__ void ob_emit_field(uint32_t field, float lane_sum, uint8_t* bits, float* part, int64_t t,
+                                              int lane) {
+    ob_store_field(field, bits, t, lane);
+    ob_store_partial(lane_sum, part, t, lane);
+}
+
+// the lane's 16 sign bits form its own 16-bit field (bit sub*4+e)
+__device__ __forceinline__ uint32_t ob_sign_field(const float (&v)[4][4]) {
+    uint32_t field = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) field |= (v[k][e] < 0.0f ? 1u : 0u) << (k * 4 + e);
+    return field;
+}
+// bits and |v| partial of tile t from the lane's 16 values; with `field` for the kernels
+// that have it before they store the values (the fused middle steps)
+__device__ __forceinline__ void ob_emit_tile(const float (&v)[4][4], uint32_t field, uint8_t* bits, float* part,
+                                             int64_t t, int lane) {
+    ob_store_field(field, bits, t, lane);
+    float ab[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ab[k][e] = __builtin_fabsf(v[k][e]);
+    ob_store_partial(lane_tree(ab), part, t, lane);
+}
+__device__ __forceinline__ void ob_emit_tile(const float (&v)[4][4], uint8_t* bits, float* part, int64_t t, int lane) {
+    ob_emit_tile(v, ob_sign_field(v), bits, part, t, lane);
+}
+
+// prologue of the fused middle steps: segment c of the p received ones decodes to
+// +-scale_c as stored in T (pos[c] / neg[c], in LDS; the caller's barrier publishes them)
+template <typename T>
+__device__ __forceinline__ void ob_scale_tables(const uint8_t* in, int64_t chunk_offset, int p, float* pos, float* neg) {
+    if (threadIdx.x < (unsigned)p) {
+        float sc;
+        __builtin_memcpy(&sc, in + (int64_t)threadIdx.x * chunk_offset, 4);
+        pos[threadIdx.x] = as_stored<T>(sc);
+        neg[threadIdx.x] = as_stored<T>(-sc);
+    }
+}
+
+// decode of the lane's field of tile t: bit ? -scale : +scale, as a sign-bit flip of the
+// scale's bits
+template <typename T, bool NTS>
+__device__ __forceinline__ void ob_decode_field(uint32_t field, uint32_t sbits, typename T::storage* dst, int64_t t,
+                                                int64_t cs, bool vec, int lane) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float f[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[e] = __uint_as_float(sbits ^ ((field << (31 - (k * 4 + e))) & 0x80000000u));
+        store4<T, NTS>(dst, t * kObTile + k * 256 + lane * 4, cs, vec, f);
+    }
+}
+
+// Body of the finalize kernels, one kObFinalizeThreads workgroup per chunk: scale =
+// F(partials) / n, the header, the slack; returns the scale to every thread
+__device__ __forceinline__ float ob_finalize(const float* partials, int64_t tiles_per_chunk, int64_t in_num_elem,
+                                             int64_t cs, int target, uint8_t* out, int64_t chunk_offset,
+                                             int64_t out_bytes, int num_chunks, float (&lvl)[2][2048]) {
+    const int c = target < 0 ? (int)blockIdx.x : target;
+    const int64_t n = ob_valid(in_num_elem, cs, c);
+    const float* part = partials + (int64_t)blockIdx.x * tiles_per_chunk;
+    const int64_t m1 = (n + kObTile - 1) / kObTile;  // tiles holding valid elements
+    const float total = chunk_tree([part](int64_t r) { return part[r]; }, m1, lvl);
+    uint8_t* seg = out + (int64_t)c * chunk_offset;
+    const float scale = n > 0 ? total / (float)n : 0.0f;
+    if (threadIdx.x < 32) {
+        const uint32_t sb = __float_as_uint(scale), nb = (uint32_t)n;
+        const int t = threadIdx.x;
+        uint32_t b = 0;
+        if (t < 4) b = (sb >> (8 * t)) & 0xff;
+        else if (t < 8) b = (nb >> (8 * (t - 4))) & 0xff;
+        seg[t] = (uint8_t)b;
+    }
+    const int64_t tiles = (cs + kObTile - 1) / kObTile;
+    for (int64_t j = 32 + tiles * kObTileBytes + threadIdx.x; j < chunk_offset; j += kObFinalizeThreads) seg[j] = 0;
+    if (target < 0 && c == num_chunks - 1)
+        for (int64_t j = (int64_t)num_chunks * chunk_offset + threadIdx.x; j < out_bytes; j += kObFinalizeThreads)
+            out[j] = 0;
+    return scale;
+}
+
+// ------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------
 static int64_t ob_tiles(int64_t cs) { return (cs + kObTile - 1) / kObTile; }
 
 static int ob_blocks(int64_t tiles, int nact, int target_blocks = kTargetBlocks) {
@@ -235,6 +342,52 @@ static int ob_blocks(int64_t tiles, int nact, int target_blocks = kTargetBlocks)
     const int64_t cap = (target_blocks + nact - 1) / nact;
     if (b > cap) b = cap;
     return (int)(b < 1 ? 1 : b);
+}
+
+// the argument checks the entries share: a segment of co bytes holds its header and tiles ...
+static inline bool ob_holds(int64_t co, int64_t tiles) { return co >= 32 + tiles * kObTileBytes; }
+// ... every segment's bit tiles are dword-aligned (they are written as dwords) ...
+static inline bool ob_aligned(const void* segs, int64_t co) { return ((uintptr_t)segs + 32) % 4 == 0 && co % 4 == 0; }
+// ... the workspace holds the tile partials of the nact chunks encoded ...
+static inline bool ob_ws_ok(const void* ws, size_t ws_bytes, int nact, int64_t tiles) {
+    return ws && ws_bytes >= (size_t)nact * (size_t)(tiles > 0 ? tiles : 1) * sizeof(float);
+}
+// ... and the error-feedback state (the carry is read and written as 16-B vectors)
+static inline bool ob_ef_state_ok(const float* carry, const float* scales) {
+    return carry && scales && (uintptr_t)carry % 16 == 0 && (uintptr_t)scales % 16 == 0;
+}
+
+// What the two encodes check alike after their own arguments, in their order of precedence:
+// p segments of co bytes each at `out`, nact of them encoded
+static inline int ob_check_encode(const uint8_t* out, int64_t co, int64_t tiles, const void* ws, size_t ws_bytes, int nact) {
+    if (!ob_holds(co, tiles)) return BAGUA_ERR_INVALID_ARG;
+    if (!ob_ws_ok(ws, ws_bytes, nact, tiles)) return BAGUA_ERR_WORKSPACE;
+    if (!ob_aligned(out, co)) return BAGUA_ERR_INVALID_ARG;
+    return BAGUA_OK;
+}
+
+// What the two fused middle steps check alike, in their order of precedence (the
+// error-feedback one checks its state first).  UNSUPPORTED: the op falls back on that code
+// to decompress + reduce + compress
+static inline int ob_check_middle(const uint8_t* recv, size_t recv_bytes, int cs, int p, const uint8_t* out, size_t out_bytes,
+                           int target, const void* ws, size_t ws_bytes) {
+    if (p <= 0 || p > kMaxFusedChunks || cs < 0 || target < 0 || target >= p || !recv || !out)
+        return BAGUA_ERR_UNSUPPORTED;
+    const int64_t co_in = (int64_t)(recv_bytes / (size_t)p), co = (int64_t)(out_bytes / (size_t)p);
+    const int64_t tiles = ob_tiles(cs);
+    if (!ob_holds(co_in, tiles) || !ob_holds(co, tiles)) return BAGUA_ERR_INVALID_ARG;
+    if (!ob_aligned(recv, co_in) || !ob_aligned(out, co)) return BAGUA_ERR_INVALID_ARG;
+    if (!ob_ws_ok(ws, ws_bytes, 1, tiles)) return BAGUA_ERR_WORKSPACE;
+    return BAGUA_OK;
+}
+
+// Non-temporal accesses for a stream of `bytes` that the next kernel reads again?  Up to
+// the 256 MiB Infinity Cache default-policy ones (the lines stay on chip for the reader);
+// past it the cache cannot keep the dirty lines, which the next kernel then writes back.
+// `knob` = 1 / 0 forces either (A/B)
+static inline bool ob_nt_by_size(int64_t bytes, const char* knob) {
+    const int env = tune_int(knob, -1);
+    return (env >= 0 ? env : (bytes > ((int64_t)256 << 20) ? 1 : 0)) == 1;
 }
 
 }  // namespace bagua

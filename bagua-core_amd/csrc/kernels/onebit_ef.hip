@@ -33,25 +33,6 @@ __device__ __forceinline__ float ef_compensate(float x, float k, float dpos, flo
     return x + r;
 }
 
-// bits, |v| partial of tile t from the lane's 16 compensated values
-__device__ __forceinline__ void ef_emit_tile(const float (&v)[4][4], uint8_t* bits, float* part, int64_t t, int lane) {
-    uint32_t field = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) field |= (v[k][e] < 0.0f ? 1u : 0u) << (k * 4 + e);
-    // even lanes store their field and the odd neighbour's as one dword
-    const uint32_t next = odd_neighbour(field);
-    if ((lane & 1) == 0) reinterpret_cast<uint32_t*>(bits + t * kObTileBytes)[lane >> 1] = field | (next << 16);
-    float ab[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ab[k][e] = __builtin_fabsf(v[k][e]);
-    const float s = wave_tree_sum_lane0(lane_tree(ab));
-    if (lane == 0) part[t] = s;
-}
-
 // ------------------------------------------------------------------------
 // worker encode: onebit_encode_kernel's tile layout (one wave per 1024-element
 // tile, the lane's 16 sign bits in registers, odd_neighbour pairing, the DPP
@@ -134,7 +115,7 @@ __global__ __launch_bounds__(kBlock) void onebit_encode_ef_kernel(
                 store4<F32, false>(kc, j, cs, kvec, v[k]);
             }
         }
-        ef_emit_tile(v, bits, part, t, lane);
+        ob_emit_tile(v, bits, part, t, lane);
     }
 }
 
@@ -147,27 +128,9 @@ __global__ __launch_bounds__(kObFinalizeThreads) void onebit_finalize_ef_kernel(
     const float* __restrict__ partials, int64_t tiles_per_chunk, int64_t in_num_elem, int64_t cs, int target,
     uint8_t* __restrict__ out, int64_t chunk_offset, int64_t out_bytes, int num_chunks, float* __restrict__ scale_out) {
     __shared__ float lvl[2][2048];
-    const int c = target < 0 ? (int)blockIdx.x : target;
-    const int64_t n = ob_valid(in_num_elem, cs, c);
-    const float* part = partials + (int64_t)blockIdx.x * tiles_per_chunk;
-    const int64_t m1 = (n + kObTile - 1) / kObTile;
-    const float total = chunk_tree([part](int64_t r) { return part[r]; }, m1, lvl);
-    uint8_t* seg = out + (int64_t)c * chunk_offset;
-    const float scale = n > 0 ? total / (float)n : 0.0f;
-    if (threadIdx.x < 32) {
-        const uint32_t sb = __float_as_uint(scale), nb = (uint32_t)n;
-        const int t = threadIdx.x;
-        uint32_t b = 0;
-        if (t < 4) b = (sb >> (8 * t)) & 0xff;
-        else if (t < 8) b = (nb >> (8 * (t - 4))) & 0xff;
-        seg[t] = (uint8_t)b;
-    }
-    if (threadIdx.x == 0) scale_out[target < 0 ? c : 0] = scale;
-    const int64_t tiles = (cs + kObTile - 1) / kObTile;
-    for (int64_t j = 32 + tiles * kObTileBytes + threadIdx.x; j < chunk_offset; j += kObFinalizeThreads) seg[j] = 0;
-    if (target < 0 && c == num_chunks - 1)
-        for (int64_t j = (int64_t)num_chunks * chunk_offset + threadIdx.x; j < out_bytes; j += kObFinalizeThreads)
-            out[j] = 0;
+    const float scale = ob_finalize(partials, tiles_per_chunk, in_num_elem, cs, target, out, chunk_offset, out_bytes,
+                                    num_chunks, lvl);
+    if (threadIdx.x == 0) scale_out[target < 0 ? blockIdx.x : 0] = scale;
 }
 
 // ------------------------------------------------------------------------
@@ -182,12 +145,7 @@ __global__ __launch_bounds__(kBlock) void onebit_reduce_encode_ef_kernel(
     const uint8_t* __restrict__ in, int64_t chunk_offset, int64_t cs, int p, float* __restrict__ carry2,
     const float* __restrict__ scale2, uint8_t* __restrict__ out_seg, float* __restrict__ part) {
     __shared__ float pos[kMaxFusedChunks], neg[kMaxFusedChunks];
-    if (threadIdx.x < (unsigned)p) {  // segment c decodes to +-scale_c as stored in T
-        float sc;
-        __builtin_memcpy(&sc, in + (int64_t)threadIdx.x * chunk_offset, 4);
-        pos[threadIdx.x] = as_stored<T>(sc);
-        neg[threadIdx.x] = as_stored<T>(-sc);
-    }
+    ob_scale_tables<T>(in, chunk_offset, p, pos, neg);
     __syncthreads();
     const float s2 = scale2[0];
     const float dpos = as_stored<T>(s2), dneg = as_stored<T>(-s2);
@@ -203,6 +161,8 @@ __global__ __launch_bounds__(kBlock) void onebit_reduce_encode_ef_kernel(
         float kk[4][4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) load4<F32>(carry2, t * kObTile + k * 256 + lane * 4, cs, true, kk[k]);
+        // the BY-wide accumulation of onebit_reduce_encode_kernel, written out in both: as a
+        // shared step it cost several instantiations an occupancy step
         float s[16][BY];
 #pragma unroll
         for (int b = 0; b < 16; ++b)
@@ -237,17 +197,13 @@ __global__ __launch_bounds__(kBlock) void onebit_reduce_encode_ef_kernel(
             }
             store4<F32, false>(carry2, t * kObTile + k * 256 + lane * 4, cs, true, v[k]);
         }
-        ef_emit_tile(v, bits, part, t, lane);
+        ob_emit_tile(v, bits, part, t, lane);
     }
 }
 
 // ------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------
-static bool ef_state_ok(const float* carry, const float* scales) {
-    return carry && scales && (uintptr_t)carry % 16 == 0 && (uintptr_t)scales % 16 == 0;
-}
-
 // stage 0: encode every tile + finalize; 1: encode tiles [t_begin, t_end) only;
 // 2: finalize only (headers, slack and the new scales from the partials)
 template <typename T>
@@ -258,28 +214,21 @@ static int ob_compress_ef_impl(const void* input, int in_num_elem, int cs, int p
     if (p <= 0 || p > 65535 || cs < 0 || !out || (!input && stage != 2) || t_begin < 0 || t_end < t_begin)
         return BAGUA_ERR_INVALID_ARG;
     if ((int64_t)in_num_elem != (int64_t)cs * p) return BAGUA_ERR_INVALID_ARG;  // every chunk fully valid
-    if (!ef_state_ok(carry, scales)) return BAGUA_ERR_INVALID_ARG;
+    if (!ob_ef_state_ok(carry, scales)) return BAGUA_ERR_INVALID_ARG;
     const int64_t co = (int64_t)(out_bytes / (size_t)p);
     const int64_t tiles = ob_tiles(cs);
-    if (co < 32 + tiles * kObTileBytes) return BAGUA_ERR_INVALID_ARG;
-    if (!ws || ws_bytes < (size_t)p * (size_t)(tiles > 0 ? tiles : 1) * sizeof(float)) return BAGUA_ERR_WORKSPACE;
-    if (((uintptr_t)out + 32) % 4 || co % 4) return BAGUA_ERR_INVALID_ARG;  // bit tiles are written as dwords
+    if (const int e = ob_check_encode(out, co, tiles, ws, ws_bytes, p)) return e;
     float* partials = static_cast<float*>(ws);
     const int64_t tb = stage == 2 ? 0 : t_begin, te = stage == 2 ? tiles : (t_end < tiles ? t_end : tiles);
     if (stage != 2 && te > tb) {
         const dim3 grid(ob_blocks(te - tb, p, tune_int("BAGUA_TUNE_OB_EF_ENCODE_BLOCKS", kObEfEncodeBlocks)), p);
-        // Carry policy by the state's size, as the plain decode's stores: up to the
-        // 256 MiB Infinity Cache default-policy accesses (the next step's encode finds
-        // the carry there), past it non-temporal ones.  BAGUA_OB_EF_CARRY_NT=1 / 0
-        // forces either (A/B).
-        const int env = tune_int("BAGUA_OB_EF_CARRY_NT", -1);
-        const int nt = env >= 0 ? env : ((int64_t)cs * p * 4 > ((int64_t)256 << 20) ? 1 : 0);
-        if (nt == 1)
-            launch(onebit_encode_ef_kernel<T, true>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input), (int64_t)cs,
-                   carry, static_cast<const float*>(scales), out, co, partials, tiles, tb, te);
-        else
-            launch(onebit_encode_ef_kernel<T, false>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
-                   (int64_t)cs, carry, static_cast<const float*>(scales), out, co, partials, tiles, tb, te);
+        // Carry policy by the state's size, as the plain decode's stores (ob_nt_by_size):
+        // the next step's encode finds a carry of up to 256 MiB in the Infinity Cache
+        with_bool(ob_nt_by_size((int64_t)cs * p * 4, "BAGUA_OB_EF_CARRY_NT"), [&](auto nt) {
+            launch(onebit_encode_ef_kernel<T, decltype(nt)::value>, grid, dim3(kBlock), 0, s,
+                   static_cast<const S*>(input), (int64_t)cs, carry, static_cast<const float*>(scales), out, co,
+                   partials, tiles, tb, te);
+        });
     }
     if (stage != 1)
         launch(onebit_finalize_ef_kernel, dim3(p), dim3(kObFinalizeThreads), 0, s, partials, tiles, (int64_t)in_num_elem,
@@ -287,38 +236,26 @@ static int ob_compress_ef_impl(const void* input, int in_num_elem, int cs, int p
     return check_launch();
 }
 
-template <typename T, int BY>
-static void launch_ob_reduce_ef(const uint8_t* in, int64_t co, int64_t cs, int p, int average, float* carry2,
-                                const float* scale2, uint8_t* seg, float* part, int blocks, hipStream_t s) {
-    if (average)
-        launch(onebit_reduce_encode_ef_kernel<T, BY, true>, dim3(blocks), dim3(kBlock), 0, s, in, co, cs, p, carry2,
-               scale2, seg, part);
-    else
-        launch(onebit_reduce_encode_ef_kernel<T, BY, false>, dim3(blocks), dim3(kBlock), 0, s, in, co, cs, p, carry2,
-               scale2, seg, part);
-}
-
 template <typename T>
 static int ob_reduce_requantize_ef_impl(const uint8_t* recv, size_t recv_bytes, int cs, int p, int average,
                                         uint8_t* out, size_t out_bytes, int target, void* ws, size_t ws_bytes,
                                         float* carry2, float* scale2, hipStream_t s) {
-    if (!ef_state_ok(carry2, scale2)) return BAGUA_ERR_INVALID_ARG;
-    if (p <= 0 || p > kMaxFusedChunks || cs < 0 || target < 0 || target >= p || !recv || !out)
-        return BAGUA_ERR_UNSUPPORTED;  // caller runs decompress + reduce + the worker encode on the own chunk
+    if (!ob_ef_state_ok(carry2, scale2)) return BAGUA_ERR_INVALID_ARG;
+    // UNSUPPORTED: the caller runs decompress + reduce + the worker encode on the own chunk
+    if (const int e = ob_check_middle(recv, recv_bytes, cs, p, out, out_bytes, target, ws, ws_bytes)) return e;
     const int64_t co_in = (int64_t)(recv_bytes / (size_t)p), co = (int64_t)(out_bytes / (size_t)p);
     const int64_t tiles = ob_tiles(cs);
-    if (co_in < 32 + tiles * kObTileBytes || co < 32 + tiles * kObTileBytes) return BAGUA_ERR_INVALID_ARG;
-    if (((uintptr_t)recv + 32) % 4 || co_in % 4 || ((uintptr_t)out + 32) % 4 || co % 4) return BAGUA_ERR_INVALID_ARG;
-    if (!ws || ws_bytes < (size_t)(tiles > 0 ? tiles : 1) * sizeof(float)) return BAGUA_ERR_WORKSPACE;
     float* part = static_cast<float*>(ws);
     uint8_t* seg = out + (int64_t)target * co;
     if (tiles > 0) {
         const int blocks = ob_blocks(tiles, 1);
-        switch (reduce_by(p)) {
-            case 2: launch_ob_reduce_ef<T, 2>(recv, co_in, cs, p, average, carry2, scale2, seg, part, blocks, s); break;
-            case 4: launch_ob_reduce_ef<T, 4>(recv, co_in, cs, p, average, carry2, scale2, seg, part, blocks, s); break;
-            default: launch_ob_reduce_ef<T, 8>(recv, co_in, cs, p, average, carry2, scale2, seg, part, blocks, s); break;
-        }
+        with_by(p, [&](auto by) {
+            with_bool(average != 0, [&](auto avg) {
+                launch(onebit_reduce_encode_ef_kernel<T, decltype(by)::value, decltype(avg)::value>, dim3(blocks),
+                       dim3(kBlock), 0, s, recv, co_in, (int64_t)cs, p, carry2, static_cast<const float*>(scale2), seg,
+                       part);
+            });
+        });
     }
     // header + slack of the own segment and the new server scale
     launch(onebit_finalize_ef_kernel, dim3(1), dim3(kObFinalizeThreads), 0, s, part, tiles, (int64_t)p * cs, (int64_t)cs,
@@ -339,36 +276,35 @@ int bagua_onebit_ef_state_bytes(int chunk_size, int num_chunks, size_t* carry_by
     return BAGUA_OK;
 }
 
-#define OB_EF_DISPATCH(dtype, CALL)                                        \
-    switch (dtype) {                                                       \
-        case BAGUA_DTYPE_F32: return CALL(F32);                            \
-        case BAGUA_DTYPE_F16: return CALL(F16);                            \
-        case BAGUA_DTYPE_BF16: return CALL(BF16);                          \
-    }                                                                      \
-    return BAGUA_ERR_INVALID_ARG /* U8, I64, U64 and unknown codes */
+// the error-feedback entries answer INVALID_ARG for U8, I64, U64 and unknown dtype codes;
+// the whole-chunk entry is stage 0 / every tile of the range entry's code
+static int ob_compress_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                          uint8_t* output, size_t output_bytes, void* workspace, size_t workspace_bytes, float* carry,
+                          float* scales, bagua_stream_t stream, int stage, int64_t tile_begin, int64_t tile_end) {
+    return with_dtype(
+        dtype,
+        [&](auto t) {
+            return ob_compress_ef_impl<decltype(t)>(input, input_num_element, chunk_size, num_chunks, output,
+                                                    output_bytes, workspace, workspace_bytes, carry, scales,
+                                                    static_cast<hipStream_t>(stream), stage, tile_begin, tile_end);
+        },
+        BAGUA_ERR_INVALID_ARG);
+}
 
 int bagua_onebit_compress_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
                              uint8_t* output, size_t output_bytes, void* workspace, size_t workspace_bytes,
                              int target_chunk, float* carry, float* scales, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (target_chunk != -1) return BAGUA_ERR_INVALID_ARG;
-#define CALL(T)                                                                                                    \
-    ob_compress_ef_impl<T>(input, input_num_element, chunk_size, num_chunks, output, output_bytes, workspace,       \
-                           workspace_bytes, carry, scales, s)
-    OB_EF_DISPATCH(dtype, CALL);
-#undef CALL
+    return ob_compress_ef(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, workspace,
+                          workspace_bytes, carry, scales, stream, 0, 0, INT64_MAX);
 }
 
 int bagua_onebit_encode_range_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
                                  uint8_t* output, size_t output_bytes, void* workspace, size_t workspace_bytes,
                                  int tile_begin, int tile_end, float* carry, const float* scales,
                                  bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define CALL(T)                                                                                                    \
-    ob_compress_ef_impl<T>(input, input_num_element, chunk_size, num_chunks, output, output_bytes, workspace,       \
-                           workspace_bytes, carry, const_cast<float*>(scales), s, 1, tile_begin, tile_end)
-    OB_EF_DISPATCH(dtype, CALL);
-#undef CALL
+    return ob_compress_ef(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, workspace,
+                          workspace_bytes, carry, const_cast<float*>(scales), stream, 1, tile_begin, tile_end);
 }
 
 int bagua_onebit_finalize_ef(const void* workspace, size_t workspace_bytes, int input_num_element, int chunk_size,
@@ -385,14 +321,15 @@ int bagua_onebit_reduce_requantize_ef(int dtype, const uint8_t* input, size_t in
                                       int num_chunks, int average, uint8_t* output, size_t output_bytes,
                                       int target_chunk, void* workspace, size_t workspace_bytes, float* carry,
                                       float* scale, bagua_stream_t stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define CALL(T)                                                                                                    \
-    ob_reduce_requantize_ef_impl<T>(input, input_bytes, chunk_size, num_chunks, average, output, output_bytes,      \
-                                    target_chunk, workspace, workspace_bytes, carry, scale, s)
-    OB_EF_DISPATCH(dtype, CALL);
-#undef CALL
+    return with_dtype(
+        dtype,
+        [&](auto t) {
+            return ob_reduce_requantize_ef_impl<decltype(t)>(input, input_bytes, chunk_size, num_chunks, average,
+                                                             output, output_bytes, target_chunk, workspace,
+                                                             workspace_bytes, carry, scale,
+                                                             static_cast<hipStream_t>(stream));
+        },
+        BAGUA_ERR_INVALID_ARG);
 }
-
-#undef OB_EF_DISPATCH
 
 }  // extern "C"
