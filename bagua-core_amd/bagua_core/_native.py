@@ -34,6 +34,7 @@ except ImportError as _e:
 # dtype / method / op codes (bagua_kernels.h, bagua_core.h)
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_U8, DTYPE_I64, DTYPE_U64 = 0, 1, 2, 3, 4, 5
 COMPRESSION_NONE, COMPRESSION_MINMAX_UINT8, COMPRESSION_ONEBIT, COMPRESSION_MXFP4 = 0, 1, 2, 3
+COMPRESSION_MXFP8 = 4
 # piece schedules (bagua_kernels.h): a count, optionally OR-ed with PIECES_TAPERED
 PIECES_COUNT_MASK, PIECES_TAPERED, PIECES_MULTIPATH, PIECES_FOLDED, PIECES_TABLES = (0xFFFF, 0x10000, 0x20000, 0x40000,
                                                                                    0x80000)
@@ -155,6 +156,14 @@ KERNEL_SIGNATURES = {
     "bagua_mxfp4_decompress_range": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _i32, _vp]),
     "bagua_mxfp4_reduce_requantize_range": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _i32,
                                                    _vp]),
+    "bagua_mxfp8_compressed_bytes": (_sz, [_i32, _i32]),
+    "bagua_mxfp8_compress": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
+    "bagua_mxfp8_decompress": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _vp]),
+    "bagua_mxfp8_reduce_requantize": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _vp, _sz, _i32, _vp]),
+    "bagua_mxfp8_piece_range": (_i32, [_i32, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "bagua_mxfp8_compress_range": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
+    "bagua_mxfp8_decompress_range": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "bagua_mxfp8_reduce_requantize_range": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _i32, _vp]),
     "bagua_mxfp4_ef_state_bytes": (_i32, [_i32, _i32, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
     "bagua_mxfp4_compress_ef": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
     "bagua_mxfp4_reduce_requantize_ef": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),

@@ -8,7 +8,7 @@ accessors.  Every codec call goes through the C ABI into the gfx950 kernels
 
 Extensions over the reference: torch.bfloat16 tensors (the reference rejects
 them, lib.rs:211-221), the "OneBitSignScale" method and the "MXFP4"
-method (MXFP4.md).
+method (MXFP4.md) and its 8-bit sibling "MXFP8" (MXFP8.md).
 """
 from __future__ import annotations
 
@@ -30,7 +30,7 @@ _DTYPE_NAMES = {code: name for code, name in _DTYPES.values()}
 _DTYPE_NAMES[N.DTYPE_U64] = "U64"
 
 METHODS = {"MinMaxUInt8": N.COMPRESSION_MINMAX_UINT8, "OneBitSignScale": N.COMPRESSION_ONEBIT,
-           "MXFP4": N.COMPRESSION_MXFP4}
+           "MXFP4": N.COMPRESSION_MXFP4, "MXFP8": N.COMPRESSION_MXFP8}
 
 
 def compression_code(method: str) -> int:

@@ -149,7 +149,7 @@ int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_
                    int sched, int average);
 enum { kOpCentralized = 1, kOpCentralizedUnfused, kOpCentralizedPipelined, kOpOneBitPipelined, kOpRing,
        kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback, kOpMxfp4Pipelined, kOpMxfp4Stochastic,
-       kOpMxfp4StochasticPipelined };
+       kOpMxfp4StochasticPipelined, kOpMxfp8Pipelined };
 
 // The alltoall of the unpieced ops: slot j of recv <- rank j's segment `rank`.  One rank
 // receives its own bytes by a device copy (RCCL's single-rank copy kernel was slower: 1 GiB
@@ -309,6 +309,12 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
                                                    send.as<uint8_t>(), k.S, k.rank, sr->server, (void*)(uintptr_t)s)
                 : bagua_mxfp4_reduce_requantize(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, nullptr, average,
                                                 send.as<uint8_t>(), k.S, k.rank, (void*)(uintptr_t)s);
+        if (rc == BAGUA_OK) done = true;
+        else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
+    } else if (fused && method == BAGUA_COMPRESSION_MXFP8 && t->num_elem == t->num_elem_allocated) {
+        // likewise (MXFP8.md)
+        rc = bagua_mxfp8_reduce_requantize(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, nullptr, average,
+                                           send.as<uint8_t>(), k.S, k.rank, (void*)(uintptr_t)s);
         if (rc == BAGUA_OK) done = true;
         else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
     }
@@ -784,11 +790,29 @@ int centralized_onebit_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
 // sr: the same schedule with both encodes stochastic (MXFP4.md, "Stochastic rounding").  A
 // word depends on the key and the element's index alone, so every piece count gives the
 // unpieced op's bytes.
+//
+// The schedule serves both block codecs (MXFP8.md, "Pipelined op"): what differs is the three
+// range entries, the piece table and the op kind.  sr: kMxfp4 only.
+struct MxCodec {
+    int method, op_kind;
+    decltype(&bagua_mxfp4_compress_range) compress_range;
+    decltype(&bagua_mxfp4_reduce_requantize_range) reduce_requantize_range;
+    decltype(&bagua_mxfp4_decompress_range) decompress_range;
+    decltype(&mxfp4_pieces) pieces;
+};
+const MxCodec kMxfp4{BAGUA_COMPRESSION_MXFP4,           kOpMxfp4Pipelined,
+                     bagua_mxfp4_compress_range,        bagua_mxfp4_reduce_requantize_range,
+                     bagua_mxfp4_decompress_range,      mxfp4_pieces};
+const MxCodec kMxfp8{BAGUA_COMPRESSION_MXFP8,           kOpMxfp8Pipelined,
+                     bagua_mxfp8_compress_range,        bagua_mxfp8_reduce_requantize_range,
+                     bagua_mxfp8_decompress_range,      mxfp8_pieces};
+
 int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int pieces,
-                                const MxSrKeys* sr = nullptr) {
+                                const MxSrKeys* sr = nullptr, const MxCodec& mx = kMxfp4) {
     Chunking k;
     if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
-    int rc = plan(c, t, BAGUA_COMPRESSION_MXFP4, &k);
+    if (sr && mx.method != BAGUA_COMPRESSION_MXFP4) return BAGUA_ERR_UNSUPPORTED;  // the keyed kernels are MXFP4's
+    int rc = plan(c, t, mx.method, &k);
     if (rc) return rc;
     const int caller = pieces;
     pieces &= BAGUA_PIECES_COUNT_MASK;
@@ -797,15 +821,14 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
     // vector paths cannot take -- decided from values equal on every rank only
     // (vec = 1: a segment is whole 32-B lines, only the chunk has to be whole 16-B vectors)
     if (pieces == 1 || k.p == 1 || !pipeline_fits(t, k, 1))
-        return centralized(c, t, average, BAGUA_COMPRESSION_MXFP4, true, sr);
+        return centralized(c, t, average, mx.method, true, sr);
     if (t->ptr % 16)  // this rank alone: the same schedule on an aligned staging copy
         return with_aligned_copy(c, {t}, [&](const std::vector<const bagua_tensor_t*>& u) {
-            return centralized_pipelined_mxfp4(c, u[0], average, caller, sr);
+            return centralized_pipelined_mxfp4(c, u[0], average, caller, sr, mx);
         });
     const int sched = op_schedule(c->cfg, pieces, caller);
     DeviceGuard guard(c->device_id);
-    if ((rc = check_schedule(c, sr ? kOpMxfp4StochasticPipelined : kOpMxfp4Pipelined, BAGUA_COMPRESSION_MXFP4, t, k.cs,
-                             sched, average)))
+    if ((rc = check_schedule(c, sr ? kOpMxfp4StochasticPipelined : mx.op_kind, mx.method, t, k.cs, sched, average)))
         return rc;
     if (c->ensure_side(4 * (size_t)pieces + 1)) return finish(c, BAGUA_ERR_HIP);
     hipStream_t s0 = c->stream;
@@ -814,7 +837,7 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
     hipEvent_t* requantised = exchanged + pieces;
     hipEvent_t* gathered = requantised + pieces;
     std::vector<Piece> tab;
-    TRY(mxfp4_pieces(k, sched, &tab));
+    TRY(mx.pieces(k, sched, &tab));
     const int dt = t->dtype, cs = (int)k.cs, p = k.p;
     void* x = (void*)(uintptr_t)t->ptr;
     OpBuffer send(c), recv(c);
@@ -829,7 +852,7 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
         if (tab[q].b < tab[q].e)
             TRY2(sr ? bagua_mxfp4_compress_sr_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, tab[q].b, tab[q].e,
                                                     sr->worker, s0)
-                    : bagua_mxfp4_compress_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, tab[q].b, tab[q].e, s0));
+                    : mx.compress_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, tab[q].b, tab[q].e, s0));
         HIP2(hipEventRecord(encoded[q], s0));
     }
     TRY2(exchange_pieces(c, k, sb, rb, tab, true, encoded, exchanged));
@@ -840,15 +863,14 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
         if (tab[q].b < tab[q].e)
             TRY2(sr ? bagua_mxfp4_reduce_requantize_sr_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, tab[q].b,
                                                              tab[q].e, sr->server, s0)
-                    : bagua_mxfp4_reduce_requantize_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, tab[q].b,
-                                                          tab[q].e, s0));
+                    : mx.reduce_requantize_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, tab[q].b, tab[q].e, s0));
         HIP2(hipEventRecord(requantised[q], s0));
     }
     // 3. allgather + decode piece by piece
     TRY2(exchange_pieces(c, k, sb, rb, tab, false, requantised, gathered));
     for (int q = 0; q < pieces; ++q) {
         HIP2(hipStreamWaitEvent(s0, gathered[q], 0));
-        if (tab[q].b < tab[q].e) TRY2(bagua_mxfp4_decompress_range(dt, sb, k.S, cs, p, x, tab[q].b, tab[q].e, s0));
+        if (tab[q].b < tab[q].e) TRY2(mx.decompress_range(dt, sb, k.S, cs, p, x, tab[q].b, tab[q].e, s0));
     }
     return finish_both(c, BAGUA_OK);
 }
@@ -946,6 +968,7 @@ int bagua_centralized_low_precision_pipelined(BaguaSingleCommunicatorC* c, const
                                               int method, int pieces) {
     if (method == BAGUA_COMPRESSION_ONEBIT) return centralized_pipelined_onebit(c, t, average, pieces);
     if (method == BAGUA_COMPRESSION_MXFP4) return centralized_pipelined_mxfp4(c, t, average, pieces);
+    if (method == BAGUA_COMPRESSION_MXFP8) return centralized_pipelined_mxfp4(c, t, average, pieces, nullptr, kMxfp8);
     if (method != BAGUA_COMPRESSION_MINMAX_UINT8) return centralized(c, t, average, method, true);
     return centralized_pipelined(c, t, average, pieces);
 }

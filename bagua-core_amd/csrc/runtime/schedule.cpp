@@ -96,14 +96,27 @@ int onebit_pieces(const Chunking& k, int sched, std::vector<Piece>* v) {
 // blocks [b, e) are the scale bytes [b, e) and the payload bytes [sbytes + 16 b, sbytes +
 // 16 e) in both phases; the ranges of the piece that ends the chunk run to the end of
 // their regions
-int mxfp4_pieces(const Chunking& k, int sched, std::vector<Piece>* v) {
+namespace {
+template <typename Range>
+int mx_block_pieces(const Chunking& k, int sched, std::vector<Piece>* v, Range&& range, size_t block_bytes) {
     const size_t nb = (k.cs + 31) / 32, sbytes = (nb + 31) / 32 * 32, co = k.S / k.p;
-    return fill_pieces(k, sched, v, bagua_mxfp4_piece_range, [&](int, int, Piece& pc) {
+    return fill_pieces(k, sched, v, range, [&](int, int, Piece& pc) {
         if (pc.b >= pc.e) return;
         const bool last = (size_t)pc.e == nb;
         pc.a2a[0] = pc.ag[0] = ByteRange{(size_t)pc.b, last ? sbytes : (size_t)pc.e};
-        pc.a2a[1] = pc.ag[1] = ByteRange{sbytes + 16 * (size_t)pc.b, last ? co : sbytes + 16 * (size_t)pc.e};
+        pc.a2a[1] = pc.ag[1] =
+            ByteRange{sbytes + block_bytes * (size_t)pc.b, last ? co : sbytes + block_bytes * (size_t)pc.e};
     });
+}
+}  // namespace
+
+int mxfp4_pieces(const Chunking& k, int sched, std::vector<Piece>* v) {
+    return mx_block_pieces(k, sched, v, bagua_mxfp4_piece_range, 16);
+}
+
+// MXFP8 (MXFP8.md): the same with 32 payload bytes per block, [sbytes + 32 b, sbytes + 32 e)
+int mxfp8_pieces(const Chunking& k, int sched, std::vector<Piece>* v) {
+    return mx_block_pieces(k, sched, v, bagua_mxfp8_piece_range, 32);
 }
 
 // ---- ring exchange schedule ------------------------------------------------
@@ -242,7 +255,7 @@ int bagua_centralized_piece_plan(int method, int dtype, int nranks, size_t chunk
     if (method == BAGUA_COMPRESSION_MINMAX_UINT8) k.S = bagua_minmax_u8_compressed_bytes(dtype, cs, nranks);
     else if (method == BAGUA_COMPRESSION_ONEBIT) k.S = bagua_onebit_compressed_bytes(cs, nranks);
     else if (method == BAGUA_COMPRESSION_MXFP4) k.S = bagua_mxfp4_compressed_bytes(cs, nranks);
-    else return -BAGUA_ERR_UNSUPPORTED;  // no pieced op
+    else return -BAGUA_ERR_UNSUPPORTED;  // no pieced op, or none this entry describes (MXFP8: MXFP8.md, "Pipelined op")
     if (!k.S) return -BAGUA_ERR_UNSUPPORTED;
     if (k.S % (size_t)k.p) return -BAGUA_ERR_INVALID_ARG;  // the ops refuse it too (alltoall alignment)
     std::vector<Piece> v;

@@ -47,6 +47,7 @@ bool valid_schedule(int pieces);
 int minmax_pieces(const Chunking& k, int sched, std::vector<Piece>* v);
 int onebit_pieces(const Chunking& k, int sched, std::vector<Piece>* v);
 int mxfp4_pieces(const Chunking& k, int sched, std::vector<Piece>* v);
+int mxfp8_pieces(const Chunking& k, int sched, std::vector<Piece>* v);
 
 constexpr int kRingMinMultipath = 6;
 

@@ -135,6 +135,9 @@ static int compress_into(const bagua_tensor_t* t, int method, int n_chunks, uint
     if (method == BAGUA_COMPRESSION_MXFP4)  // single pass, no workspace
         return bagua_mxfp4_compress(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)cs, n_chunks,
                                     (uint8_t*)(uintptr_t)out_ptr, out_bytes, target, s);
+    if (method == BAGUA_COMPRESSION_MXFP8)  // likewise
+        return bagua_mxfp8_compress(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)cs, n_chunks,
+                                    (uint8_t*)(uintptr_t)out_ptr, out_bytes, target, s);
     return BAGUA_ERR_UNSUPPORTED;
 }
 
@@ -161,6 +164,7 @@ size_t bagua_compressed_size(int method, int dtype, size_t n_chunks, size_t chun
         return bagua_minmax_u8_compressed_bytes(dtype, (int)chunk_size, (int)n_chunks);
     if (method == BAGUA_COMPRESSION_ONEBIT) return bagua_onebit_compressed_bytes((int)chunk_size, (int)n_chunks);
     if (method == BAGUA_COMPRESSION_MXFP4) return bagua_mxfp4_compressed_bytes((int)chunk_size, (int)n_chunks);
+    if (method == BAGUA_COMPRESSION_MXFP8) return bagua_mxfp8_compressed_bytes((int)chunk_size, (int)n_chunks);
     return 0;
 }
 
@@ -316,6 +320,9 @@ int bagua_tensor_decompress_from(const bagua_tensor_t* t, int method, int n_chun
                                        (void*)(uintptr_t)t->ptr, s);
     if (method == BAGUA_COMPRESSION_MXFP4)
         return bagua_mxfp4_decompress(t->dtype, (const uint8_t*)(uintptr_t)compressed->ptr, in_bytes, (int)cs, n_chunks,
+                                      (void*)(uintptr_t)t->ptr, s);
+    if (method == BAGUA_COMPRESSION_MXFP8)
+        return bagua_mxfp8_decompress(t->dtype, (const uint8_t*)(uintptr_t)compressed->ptr, in_bytes, (int)cs, n_chunks,
                                       (void*)(uintptr_t)t->ptr, s);
     return BAGUA_ERR_UNSUPPORTED;
 }

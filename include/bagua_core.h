@@ -31,7 +31,7 @@ enum { BAGUA_DTYPE_U8 = 3, BAGUA_DTYPE_I64 = 4, BAGUA_DTYPE_U64 = 5 };
 
 /* compression methods: "MinMaxUInt8" (datatypes/mod.rs:744-747), the 1-bit and the MXFP4 extensions */
 enum { BAGUA_COMPRESSION_NONE = 0, BAGUA_COMPRESSION_MINMAX_UINT8 = 1, BAGUA_COMPRESSION_ONEBIT = 2,
-       BAGUA_COMPRESSION_MXFP4 = 3 };
+       BAGUA_COMPRESSION_MXFP4 = 3, BAGUA_COMPRESSION_MXFP8 = 4 };
 
 /* reduction ops, Aluminum/BaguaReductionOp numbering (datatypes/mod.rs:24-38) */
 enum { BAGUA_OP_SUM = 0, BAGUA_OP_PROD = 1, BAGUA_OP_MIN = 2, BAGUA_OP_MAX = 3, BAGUA_OP_AVG = 10 };

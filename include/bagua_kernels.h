@@ -268,6 +268,37 @@ int bagua_mxfp4_reduce_requantize_range(int dtype, const uint8_t* input, size_t 
                                         int num_chunks, int average, uint8_t* output, size_t output_bytes,
                                         int target_chunk, int block_begin, int block_end, bagua_stream_t stream);
 
+/* ======================================================================== */
+/* v2 — MXFP8 block-scaled 8-bit codec (extension; format in MXFP8.md)       */
+/* ======================================================================== */
+/* OCP MXFP8: 32 E4M3 elements under one power-of-two scale byte.  Per chunk: align32(nb)
+ * scale bytes, then 32 * nb payload bytes (element j of a block is payload byte j), nb =
+ * ceil(chunk_size / 32); S = num_chunks * that.  Single-pass kernels, no workspace.
+ * Segments lie at that fixed stride: the buffers must hold at least S bytes
+ * (BAGUA_ERR_INVALID_ARG otherwise) and be 16-B aligned.  The entries mirror their MXFP4
+ * namesakes above: the same arguments, status codes, piece rule (a granule of 128 blocks;
+ * payload bytes [sbytes + 32 bb, sbytes + 32 be) of each segment) and refusals.
+ * bagua_mxfp8_reduce_requantize is byte for byte bagua_mxfp8_decompress +
+ * bagua_reduce_chunks + bagua_mxfp8_compress(target) on a fully valid tensor; `tensor` may
+ * be NULL (the reduced chunk is not stored); BAGUA_ERR_UNSUPPORTED for num_chunks > 16. */
+size_t bagua_mxfp8_compressed_bytes(int chunk_size, int num_chunks);
+int bagua_mxfp8_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                         uint8_t* output, size_t output_bytes, int target_chunk, bagua_stream_t stream);
+int bagua_mxfp8_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                           void* output, bagua_stream_t stream);
+int bagua_mxfp8_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                                  void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
+                                  bagua_stream_t stream);
+int bagua_mxfp8_piece_range(int chunk_size, int pieces, int piece, int* block_begin, int* block_end);
+int bagua_mxfp8_compress_range(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                               uint8_t* output, size_t output_bytes, int block_begin, int block_end,
+                               bagua_stream_t stream);
+int bagua_mxfp8_decompress_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                                 void* output, int block_begin, int block_end, bagua_stream_t stream);
+int bagua_mxfp8_reduce_requantize_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                        int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                        int target_chunk, int block_begin, int block_end, bagua_stream_t stream);
+
 /* MXFP4 with error feedback (MXFP4.md, "Error feedback"): the same wire format, plus
  * caller-owned f32 state, zero before the first step, that carries each step's
  * quantisation error into the next.  The state is the residual itself: worker
