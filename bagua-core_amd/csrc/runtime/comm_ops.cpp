@@ -1042,6 +1042,18 @@ int bagua_centralized_full_precision_synchronous(BaguaSingleCommunicatorC* c, co
     return finish(c, rc);
 }
 
+// The fused ring kernels of a block codec (mxfp4_ring.hip, mxfp8_ring.hip: the same three
+// entries) and the switch that turns them off
+struct MxRing {
+    const char* fused_env;
+    decltype(&bagua_ring_mix_mxfp4) mix;
+    decltype(&bagua_ring_apply_mxfp4) apply;
+    decltype(&bagua_ring_one_rank_mxfp4) one_rank;
+};
+static const MxRing kMxfp4Ring{"BAGUA_MXFP4_RING_FUSED", bagua_ring_mix_mxfp4, bagua_ring_apply_mxfp4,
+                               bagua_ring_one_rank_mxfp4};
+static const MxRing kMxfp8Ring{"BAGUA_MXFP8_RING_FUSED", bagua_ring_mix_mxfp8, bagua_ring_apply_mxfp8,
+                               bagua_ring_one_rank_mxfp8};
 
 static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, const bagua_tensor_t* weight,
                          const bagua_tensor_t* left, const bagua_tensor_t* right, int method, bool allow_fused,
@@ -1056,13 +1068,18 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
     const int n = (int)t->num_elem_allocated;
     const size_t S = bagua_compressed_size(method, t->dtype, 1, t->num_elem_allocated);
     if (!S) return BAGUA_ERR_UNSUPPORTED;
-    // fused kernels (csrc/kernels/decentralized.hip, mxfp4_ring.hip) for fully valid,
-    // same-shape MinMax and MXFP4 buckets; anything else runs the reference's op sequence.
+    // fused kernels (csrc/kernels/decentralized.hip, mxfp4_ring.hip, mxfp8_ring.hip) for fully
+    // valid, same-shape MinMax, MXFP4 and MXFP8 buckets; anything else runs the reference's op
+    // sequence.
     // The choice (and with it the pipelined exchange schedule) depends only on values equal
     // on every rank; a rank whose tensors are not 16-B aligned runs on aligned copies.
-    // BAGUA_MXFP4_RING_FUSED=0 (read per call, A/B): the op sequence for MXFP4.  It changes
-    // no byte on the wire and MXFP4 is never pipelined, so ranks need not agree on it.
-    const bool mx = method == BAGUA_COMPRESSION_MXFP4 && env_int("BAGUA_MXFP4_RING_FUSED", 1) != 0;
+    // BAGUA_MXFP4_RING_FUSED=0 / BAGUA_MXFP8_RING_FUSED=0 (read per call, A/B): the op sequence
+    // for that block codec.  It changes no byte on the wire and neither codec is ever
+    // pipelined, so ranks need not agree on it.
+    const MxRing* mx = method == BAGUA_COMPRESSION_MXFP4   ? &kMxfp4Ring
+                       : method == BAGUA_COMPRESSION_MXFP8 ? &kMxfp8Ring
+                                                           : nullptr;
+    if (mx && env_int(mx->fused_env, 1) == 0) mx = nullptr;
     bool fused = allow_fused && (method == BAGUA_COMPRESSION_MINMAX_UINT8 || mx) &&
                  t->num_elem == t->num_elem_allocated;
     for (const bagua_tensor_t* o : {weight, left, right})
@@ -1078,15 +1095,15 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
     const int sched = op_schedule(c->cfg, pieces, caller);
     const bool multipath =
         (caller & BAGUA_PIECES_MULTIPATH) ? (int)c->nranks >= kRingMinMultipath : ring_multipath_enabled(c);
-    // (MXFP4 stays unpieced: one mix, one exchange, one apply, whatever the schedule asks for)
+    // (the block codecs stay unpieced: one mix, one exchange, one apply, whatever the schedule asks for)
     const bool pipelined = fused && !mx && (pieces > 1 || multipath);
     if ((rc = check_schedule(c, pipelined ? kOpRingPipelined : (allow_fused ? kOpRing : kOpRingUnfused), method, t,
                              (uint64_t)n, pipelined ? sched | (multipath ? BAGUA_PIECES_MULTIPATH : 0) : 1, 1)))
         return rc;
     if (mx && fused && c->nranks == 1 && env_int("BAGUA_ONE_RANK_FUSED", 1) != 0) {
-        // one rank: one pass over the four tensors, no payload (bagua_ring_one_rank_mxfp4)
-        rc = bagua_ring_one_rank_mxfp4(t->dtype, (void*)(uintptr_t)t->ptr, (void*)(uintptr_t)weight->ptr,
-                                       (void*)(uintptr_t)left->ptr, (void*)(uintptr_t)right->ptr, n, sp);
+        // one rank: one pass over the four tensors, no payload (bagua_ring_one_rank_mxfp4 / _mxfp8)
+        rc = mx->one_rank(t->dtype, (void*)(uintptr_t)t->ptr, (void*)(uintptr_t)weight->ptr,
+                          (void*)(uintptr_t)left->ptr, (void*)(uintptr_t)right->ptr, n, sp);
         if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
     }
     if (fused && !mx && !pipelined && c->nranks == 1 && env_int("BAGUA_ONE_RANK_FUSED", 1) != 0) {
@@ -1116,7 +1133,7 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
     if (fused && mx) {
         // :45-64 in one pass: the segment of the mixed t, which itself is never stored (every
         // path below overwrites t before anything reads it)
-        rc = bagua_ring_mix_mxfp4(t->dtype, tp, lp, rp, wp, n, mine.as<uint8_t>(), S, sp);
+        rc = mx->mix(t->dtype, tp, lp, rp, wp, n, mine.as<uint8_t>(), S, sp);
         if (rc == BAGUA_OK) mixed = true;
         else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
     } else if (fused) {
@@ -1197,7 +1214,7 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
     const bagua_tensor_t* from_r = p > 1 ? &rv : &mv;
     // :126-151
     if (fused) {
-        rc = (mx ? bagua_ring_apply_mxfp4 : bagua_ring_apply_minmax)(
+        rc = (mx ? mx->apply : bagua_ring_apply_minmax)(
             t->dtype, mine.as<uint8_t>(), (const uint8_t*)(uintptr_t)from_l->ptr,
             (const uint8_t*)(uintptr_t)from_r->ptr, S, n, tp, wp, lp, rp, sp);
         if (rc == BAGUA_OK) return finish(c, BAGUA_OK);

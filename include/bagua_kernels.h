@@ -380,6 +380,20 @@ int bagua_ring_apply_mxfp4(int dtype, const uint8_t* mine, const uint8_t* from_l
 int bagua_ring_one_rank_mxfp4(int dtype, void* tensor, void* weight, void* left, void* right, int num_elem,
                               bagua_stream_t stream);
 
+/* The same three steps with the MXFP8 codec (MXFP8.md, "Ring op"): the segment is
+ * bagua_mxfp8_compressed_bytes(num_elem, 1) bytes, the mix encodes as bagua_mxfp8_compress
+ * (num_chunks = 1) and the apply decodes as bagua_mxfp8_decompress would, scale byte 0xFF and
+ * element magnitude 0x7F included.  Arguments, results and refusals are their MXFP4
+ * namesakes', except that the apply's inputs must be 8-B aligned (the decode's rule for every
+ * dtype; the f32 kernel itself loads 4-B words). */
+int bagua_ring_mix_mxfp8(int dtype, const void* tensor, const void* left, const void* right, const void* weight,
+                         int num_elem, uint8_t* output, size_t output_bytes, bagua_stream_t stream);
+int bagua_ring_apply_mxfp8(int dtype, const uint8_t* mine, const uint8_t* from_left, const uint8_t* from_right,
+                           size_t compressed_bytes, int num_elem, void* tensor, void* weight, void* left, void* right,
+                           bagua_stream_t stream);
+int bagua_ring_one_rank_mxfp8(int dtype, void* tensor, void* weight, void* left, void* right, int num_elem,
+                              bagua_stream_t stream);
+
 /* ======================================================================== */
 /* v2 — chunk reduction and elementwise ops                                  */
 /* ======================================================================== */

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Measurement: the decentralized ring op with the MXFP4 codec, fused kernels beside the
-composed op sequence (MXFP4.md, "Ring op").
+"""Measurement: the decentralized ring op with a block codec (--codec mxfp4, the default, or
+mxfp8), fused kernels beside the composed op sequence (MXFP4.md / MXFP8.md, "Ring op").
+CODECS holds what differs between the two: the method, the switch that turns the fused kernels
+off (<SWITCH> below) and the prefix of the kernel names (<codec> below).
 
 Two buckets: 2^26 f32 elements (256 MiB) and 2^27 bf16 elements, each with its weight and
 the two peer weights.  The op runs through its normal entry on loopback communicators, at
@@ -12,9 +14,9 @@ median of 20, all variants interleaved step by step in one run.  Before every ca
 tensors are restored from pristine copies, so every variant sees the same values and the
 same cache state (the tail of the last copy, at most).
 
-  p = 1  one_rank   mxfp4_ring_one_rank_kernel (BAGUA_ONE_RANK_FUSED=1, the default)
-         mix_apply  mxfp4_ring_mix_kernel + mxfp4_ring_apply_kernel (BAGUA_ONE_RANK_FUSED=0)
-         composed   BAGUA_MXFP4_RING_FUSED=0: 3 x addmul, encode, 3 x (decode, add)
+  p = 1  one_rank   <codec>_ring_one_rank_kernel (BAGUA_ONE_RANK_FUSED=1, the default)
+         mix_apply  <codec>_ring_mix_kernel + <codec>_ring_apply_kernel (BAGUA_ONE_RANK_FUSED=0)
+         composed   <SWITCH>=0: 3 x addmul, encode, 3 x (decode, add)
   p = 2  mix_apply, composed
 
 The yardstick is the composed sequence in the same run.  Its eleventh step, the clone W = t,
@@ -22,9 +24,11 @@ is a device-to-device copy that the hook does not see, so the composed kernel su
 out (the fused kernels write W themselves); at one rank the whole call is timed as well,
 device events around it on the op's stream, and that figure includes the copy.  A kernel's
 roofline share is its algorithmic bytes over its time against 8 TB/s.  Writes the record to
---out and, for a file under profiles/, its index line in profiles/README.md.
+--out and, for a file under profiles/, its index line in profiles/README.md.  --package names
+another build of bagua-core_amd (its bagua_core/ and lib/) to measure in place of the tree's:
+an A/B of two builds is two such runs, alternated.
 
-    python tools/mxfp4_ring_probe.py [--out profiles/r10_mxfp4_ring.json]
+    python tools/mxfp4_ring_probe.py [--codec mxfp8] [--out profiles/r10_mxfp4_ring.json]
 """
 import argparse
 import ctypes
@@ -38,10 +42,9 @@ import threading
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "bagua-core_amd"))
 
 PEAK_TB_S = 8.0
-INDEX = ("| `{name}` | MXFP4 ring op, fused kernels against the composed sequence in the same run, per kernel, median "
+INDEX = ("| `{name}` | {codec} ring op, fused kernels against the composed sequence in the same run, per kernel, median "
          "of {reps}: 256 MiB f32 one rank {f1:.1f} µs in one kernel against {fc:.1f} µs composed ({fr:.2f}), two "
          "ranks mix {fm:.1f} + apply {fa:.1f} µs against {fc2:.1f} µs ({fr2:.2f}); 2^27 bf16 one rank {b1:.1f} "
          "against {bcm:.1f} µs ({br:.2f}), two ranks {bm:.1f} + {ba:.1f} against {bc2:.1f} µs ({br2:.2f}) | "
@@ -54,39 +57,51 @@ def hip_runtime_version() -> int:
     return v.value
 
 
-def kernel_bytes(kernel, n, esz, S):
-    """algorithmic bytes of one launch on a bucket of n elements"""
-    return {"mxfp4_ring_one_rank_kernel": 8 * n * esz,
-            "mxfp4_ring_mix_kernel": 4 * n * esz + S,
-            "mxfp4_ring_apply_kernel": 3 * S + 7 * n * esz,
-            "binary_kernel": 3 * n * esz,
-            "mxfp4_encode_kernel": n * esz + S,
-            "mxfp4_decode_kernel": S + n * esz}[kernel]
-
-
-COMPOSED = ["binary_kernel"] * 3 + ["mxfp4_encode_kernel"] + ["mxfp4_decode_kernel", "binary_kernel"] * 3
-VARIANTS = {
-    "one_rank": ({"BAGUA_ONE_RANK_FUSED": "1"}, ["mxfp4_ring_one_rank_kernel"]),
-    "mix_apply": ({"BAGUA_ONE_RANK_FUSED": "0"}, ["mxfp4_ring_mix_kernel", "mxfp4_ring_apply_kernel"]),
-    "composed": ({"BAGUA_MXFP4_RING_FUSED": "0"}, COMPOSED),
+# per codec: the method of the op, the switch that turns the fused kernels off, the prefix of
+# the kernel names, the entry that sizes a segment and the default record
+CODECS = {
+    "mxfp4": ("COMPRESSION_MXFP4", "BAGUA_MXFP4_RING_FUSED", "mxfp4", "bagua_mxfp4_compressed_bytes",
+              "r10_mxfp4_ring.json"),
+    "mxfp8": ("COMPRESSION_MXFP8", "BAGUA_MXFP8_RING_FUSED", "mxfp8", "bagua_mxfp8_compressed_bytes",
+              "r14_mxfp8_ring.json"),
 }
 
 
-def measure(bc, N, dtype_code, tdtype, esz, n, p, variants, warmup, reps):
+def kernel_bytes(kernel, prefix, n, esz, S):
+    """algorithmic bytes of one launch on a bucket of n elements; prefix: the codec's, with its underscore"""
+    return {"ring_one_rank_kernel": 8 * n * esz,
+            "ring_mix_kernel": 4 * n * esz + S,
+            "ring_apply_kernel": 3 * S + 7 * n * esz,
+            "binary_kernel": 3 * n * esz,
+            "encode_kernel": n * esz + S,
+            "decode_kernel": S + n * esz}[kernel.removeprefix(prefix)]
+
+
+def variants_of(codec):
+    """variant -> (environment, the kernels it launches, in order)"""
+    _, switch, k, _, _ = CODECS[codec]
+    composed = ["binary_kernel"] * 3 + [f"{k}_encode_kernel"] + [f"{k}_decode_kernel", "binary_kernel"] * 3
+    return {"one_rank": ({"BAGUA_ONE_RANK_FUSED": "1"}, [f"{k}_ring_one_rank_kernel"]),
+            "mix_apply": ({"BAGUA_ONE_RANK_FUSED": "0"}, [f"{k}_ring_mix_kernel", f"{k}_ring_apply_kernel"]),
+            "composed": ({switch: "0"}, composed)}
+
+
+def measure(bc, N, codec, tdtype, esz, n, p, variants, warmup, reps):
     from bagua_core.communicator import loopback_communicators
     dev = torch.device("cuda", 0)
     comms = loopback_communicators(p, 0)
+    vtab, method = variants_of(codec), getattr(N, CODECS[codec][0])
     gen = torch.Generator(device=dev).manual_seed(11)
     pristine = [[(torch.randn(n, device=dev, generator=gen) * 1e-3).to(tdtype) for _ in range(4)] for _ in range(p)]
     work = [[torch.empty_like(x) for x in rank] for rank in pristine]
     raws = [[bc.BaguaTensorPy(x, f"r{r}.{k}").raw() for k, x in enumerate(work[r])] for r in range(p)]
-    S = N.K.bagua_mxfp4_compressed_bytes(n, 1)
+    S = getattr(N.K, CODECS[codec][3])(n, 1)
     st0 = torch.cuda.ExternalStream(comms[0].stream_ptr())
-    times = {v: [[] for _ in VARIANTS[v][1]] for v in variants}
+    times = {v: [[] for _ in vtab[v][1]] for v in variants}
     calls = {v: [] for v in variants}
 
     def step(variant, keep):
-        env, kernels = VARIANTS[variant]
+        env, kernels = vtab[variant]
         for r in range(p):
             for x, src in zip(work[r], pristine[r]):
                 x.copy_(src)
@@ -105,7 +120,7 @@ def measure(bc, N, dtype_code, tdtype, esz, n, p, variants, warmup, reps):
                 if r == 0:
                     N.time_next_kernels(evs)
                     whole[0].record(st0)
-                rc = N.C.bagua_decentralized_low_precision_synchronous(comms[r].handle, *refs, N.COMPRESSION_MXFP4)
+                rc = N.C.bagua_decentralized_low_precision_synchronous(comms[r].handle, *refs, method)
                 if r == 0:
                     whole[1].record(st0)
                     names.extend(N.timed_kernel_names())
@@ -136,8 +151,8 @@ def measure(bc, N, dtype_code, tdtype, esz, n, p, variants, warmup, reps):
     rec = {"elements": n, "ranks": p, "bytes_per_element": esz, "segment_bytes": int(S)}
     for v in variants:
         ks = []
-        for kernel, ts in zip(VARIANTS[v][1], times[v]):
-            med, nbytes = statistics.median(ts), kernel_bytes(kernel, n, esz, S)
+        for kernel, ts in zip(vtab[v][1], times[v]):
+            med, nbytes = statistics.median(ts), kernel_bytes(kernel, CODECS[codec][2] + "_", n, esz, S)
             rate = nbytes / (med * 1e-6) / 1e12
             ks.append({"kernel": kernel, "us": round(med, 2), "min_us": round(min(ts), 2), "max_us": round(max(ts), 2),
                        "bytes": int(nbytes), "tb_per_s": round(rate, 3), "roofline_share": round(rate / PEAK_TB_S, 3)})
@@ -146,7 +161,7 @@ def measure(bc, N, dtype_code, tdtype, esz, n, p, variants, warmup, reps):
             rec[v]["call_us"] = round(statistics.median(calls[v]), 2)
     for v in variants:
         if v != "composed":
-            rec[v]["kernel_sum_over_composed"] = round(rec[v]["kernel_sum_us"] / rec["composed"]["kernel_sum_us"], 3)
+            rec[v]["kernel_sum_over_composed"] = round(rec[v]["kernel_sum_us"] / rec["composed"]["kernel_sum_us"], 4)
     return rec
 
 
@@ -166,7 +181,8 @@ def write_index(rec, out):
     def us(r, v, i=None):
         return r[v]["kernel_sum_us"] if i is None else r[v]["kernels"][i]["us"]
 
-    row = INDEX.format(name=name, reps=rec["reps"], f1=us(f1, "one_rank"), fc=us(f1, "composed"),
+    row = INDEX.format(name=name, codec=rec["probe"].split("_")[0].upper(), reps=rec["reps"],
+                       f1=us(f1, "one_rank"), fc=us(f1, "composed"),
                        fr=f1["one_rank"]["kernel_sum_over_composed"], fm=us(f2, "mix_apply", 0), fa=us(f2, "mix_apply", 1),
                        fc2=us(f2, "composed"), fr2=f2["mix_apply"]["kernel_sum_over_composed"],
                        b1=us(b1, "one_rank"), bcm=us(b1, "composed"), br=b1["one_rank"]["kernel_sum_over_composed"],
@@ -182,27 +198,32 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--log2n-f32", type=int, default=26)
     ap.add_argument("--log2n-bf16", type=int, default=27)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10_mxfp4_ring.json"))
+    ap.add_argument("--codec", choices=sorted(CODECS), default="mxfp4")
+    ap.add_argument("--out", default=None, help="default: the codec's record under profiles/")
+    ap.add_argument("--package", default=os.path.join(ROOT, "bagua-core_amd"), help="the build to measure")
     ap.add_argument("--index", default=None, help="write the index row of an existing record and exit")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", CODECS[args.codec][4])
     if args.index:
         write_index(json.load(open(args.index)), args.index)
         return
     assert torch.cuda.is_available(), "the probe measures on the GPU; there is no fallback"
+    sys.path.insert(0, os.path.abspath(args.package))
     import bagua_core as bc
     from bagua_core import _native as N
-    for k in ("BAGUA_ONE_RANK_FUSED", "BAGUA_MXFP4_RING_FUSED"):
+    for k in ("BAGUA_ONE_RANK_FUSED", CODECS[args.codec][1]):
         os.environ.pop(k, None)
-    rec = {"probe": "mxfp4_ring", "warmup": args.warmup, "reps": args.reps,
+    rec = {"probe": args.codec + "_ring", "package": os.path.relpath(os.path.abspath(args.package), ROOT),
+           "warmup": args.warmup, "reps": args.reps,
            "timing": "per kernel (bagua_time_next_kernels) on rank 0, median; variants interleaved per step; the "
                      "composed sequence's clone W = t is a copy the hook does not see (call_us includes it)",
            "peak_tb_per_s": PEAK_TB_S, "device": torch.cuda.get_device_name(0),
            "hip_runtime_version": hip_runtime_version(), "torch_hip": torch.version.hip}
     one, two = ("one_rank", "mix_apply", "composed"), ("mix_apply", "composed")
-    for name, code, tdtype, esz, n in (("f32", N.DTYPE_F32, torch.float32, 4, 1 << args.log2n_f32),
-                                       ("bf16", N.DTYPE_BF16, torch.bfloat16, 2, 1 << args.log2n_bf16)):
-        rec[f"{name}_p1"] = measure(bc, N, code, tdtype, esz, n, 1, one, args.warmup, args.reps)
-        rec[f"{name}_p2"] = measure(bc, N, code, tdtype, esz, n, 2, two, args.warmup, args.reps)
+    for name, tdtype, esz, n in (("f32", torch.float32, 4, 1 << args.log2n_f32),
+                                 ("bf16", torch.bfloat16, 2, 1 << args.log2n_bf16)):
+        rec[f"{name}_p1"] = measure(bc, N, args.codec, tdtype, esz, n, 1, one, args.warmup, args.reps)
+        rec[f"{name}_p2"] = measure(bc, N, args.codec, tdtype, esz, n, 2, two, args.warmup, args.reps)
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
