@@ -70,6 +70,7 @@ BUCKET_OP_DECENTRALIZED_LOW_PRECISION, BUCKET_OP_CALLBACK = 3, 4
 BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK = 5
 BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK = 6
 BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC = 7
+BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK = 8
 STATUS_INVALID_ARG = 1
 
 _T = ctypes.POINTER(bagua_tensor_t)
@@ -160,6 +161,9 @@ KERNEL_SIGNATURES = {
     "bagua_mxfp8_compress": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
     "bagua_mxfp8_decompress": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _vp]),
     "bagua_mxfp8_reduce_requantize": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _vp, _sz, _i32, _vp]),
+    "bagua_mxfp8_ef_state_bytes": (_i32, [_i32, _i32, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "bagua_mxfp8_compress_ef": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
+    "bagua_mxfp8_reduce_requantize_ef": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
     "bagua_mxfp8_piece_range": (_i32, [_i32, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "bagua_mxfp8_compress_range": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "bagua_mxfp8_decompress_range": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _i32, _vp]),
@@ -231,6 +235,7 @@ CORE_SIGNATURES = {
     "bagua_tensor_compress_into": (_i32, [_T, _i32, _i32, _u64, _i32, _T]),
     "bagua_tensor_compress_error_feedback": (_i32, [_T, _i32, _u64, _T, _T, _T]),
     "bagua_tensor_compress_mxfp4_error_feedback": (_i32, [_T, _i32, _u64, _T, _T]),
+    "bagua_tensor_compress_mxfp8_error_feedback": (_i32, [_T, _i32, _u64, _T, _T]),
     "bagua_tensor_compress_mxfp4_stochastic": (_i32, [_T, _i32, _u64, _u64, _u64, _T]),
     "bagua_tensor_decompress_from": (_i32, [_T, _i32, _i32, _T, _u64]),
     "bagua_tensor_reduce_inplace": (_i32, [_T, _i32, _i32, _i32, _u64]),
@@ -272,6 +277,7 @@ CORE_SIGNATURES = {
     "bagua_centralized_low_precision_pipelined": (_i32, [_C, _T, _i32, _i32, _i32]),
     "bagua_centralized_onebit_error_feedback": (_i32, [_C, _T, _i32, _T, _T, _T, _T, _i32]),
     "bagua_centralized_mxfp4_error_feedback": (_i32, [_C, _T, _i32, _T, _T]),
+    "bagua_centralized_mxfp8_error_feedback": (_i32, [_C, _T, _i32, _T, _T]),
     "bagua_centralized_mxfp4_stochastic": (_i32, [_C, _T, _i32, _u64, _u64, _i32]),
     "bagua_centralized_full_precision_synchronous": (_i32, [_C, _T, _i32]),
     "bagua_decentralized_low_precision_synchronous": (_i32, [_C, _T, _T, _T, _T, _i32]),

@@ -11,6 +11,7 @@ on the communicator's stream:
   CentralizedOneBitErrorFeedback       -> bagua_centralized_onebit_error_feedback
   CentralizedMXFP4ErrorFeedback        -> bagua_centralized_mxfp4_error_feedback
   CentralizedMXFP4Stochastic           -> bagua_centralized_mxfp4_stochastic
+  CentralizedMXFP8ErrorFeedback        -> bagua_centralized_mxfp8_error_feedback
   CentralizedFullPrecisionSynchronous  -> bagua_centralized_full_precision_synchronous
   DecentralizedLowPrecisionSynchronous -> bagua_decentralized_low_precision_synchronous
   PythonOp                             -> a ctypes callback (python_ffi_op.rs)
@@ -30,7 +31,7 @@ from typing import Callable, Optional
 from . import _native as N
 from .communicator import BaguaSingleCommunicatorPy
 from .tensor import (_DTYPES, BaguaTensorPy, MXFP4ErrorFeedbackState, MXFP4StochasticRounding,
-                     OneBitErrorFeedbackState, compression_code)
+                     MXFP8ErrorFeedbackState, OneBitErrorFeedbackState, compression_code)
 
 CALLBACK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_char_p)
 
@@ -104,9 +105,28 @@ class CentralizedMXFP4Stochastic:
                                       comm=_handle(self.communicator), sr_seed=self.rounding.seed)
 
 
+@dataclass
+class CentralizedMXFP8ErrorFeedback:
+    """the "MXFP8" centralized op carrying its quantisation error from step to step in
+    `state` (kept alive with the op); the residuals travel in the two carry fields"""
+    communicator: BaguaSingleCommunicatorPy
+    average: bool
+    state: MXFP8ErrorFeedbackState
+    compression: str = "MXFP8"
+
+    def native(self) -> N.bagua_bucket_op_t:
+        st = self.state
+        return N.bagua_bucket_op_t(kind=N.BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK, average=int(self.average),
+                                   compression=compression_code(self.compression), fused=1,
+                                   comm=_handle(self.communicator), ef_worker_carry=st._raw(st.worker_residual),
+                                   ef_server_carry=st._raw(st.server_residual))
+
+
 # the state class of each codec that has error feedback, and the op it appends
 _EF_CODECS = {"OneBitSignScale": (OneBitErrorFeedbackState, CentralizedOneBitErrorFeedback),
-              "MXFP4": (MXFP4ErrorFeedbackState, CentralizedMXFP4ErrorFeedback)}
+              "MXFP4": (MXFP4ErrorFeedbackState, CentralizedMXFP4ErrorFeedback),
+              "MXFP8": (MXFP8ErrorFeedbackState, CentralizedMXFP8ErrorFeedback)}
+_EF_STATES = tuple(state_cls for state_cls, _ in _EF_CODECS.values())
 
 
 @dataclass
@@ -232,7 +252,8 @@ class BaguaBucketPy:
                                           error_feedback=None, stochastic_rounding=None) -> None:
         """error_feedback (keyword; not hierarchical): the state that carries the op's
         quantisation error from one execution to the next -- a OneBitErrorFeedbackState with
-        "OneBitSignScale", an MXFP4ErrorFeedbackState with "MXFP4".
+        "OneBitSignScale", an MXFP4ErrorFeedbackState with "MXFP4", an MXFP8ErrorFeedbackState
+        with "MXFP8".
 
         stochastic_rounding (keyword; "MXFP4" only, not hierarchical, not together with
         error_feedback): an MXFP4StochasticRounding.  Both encodes of the op round at random
@@ -272,10 +293,10 @@ class BaguaBucketPy:
 
     def _append_error_feedback(self, comm, hierarchical, average, compression, state) -> None:
         if compression not in _EF_CODECS:
-            raise NotImplementedError(f"error feedback exists for the OneBitSignScale and MXFP4 codecs only, not for "
-                                      f"compression={compression!r}")
+            raise NotImplementedError(f"error feedback exists for the OneBitSignScale, MXFP4 and MXFP8 codecs only, "
+                                      f"not for compression={compression!r}")
         state_cls, op_cls = _EF_CODECS[compression]
-        if isinstance(state, (OneBitErrorFeedbackState, MXFP4ErrorFeedbackState)) and not isinstance(state, state_cls):
+        if isinstance(state, _EF_STATES) and not isinstance(state, state_cls):
             raise NotImplementedError(f"compression={compression!r} takes a {state_cls.__name__}, not a "
                                       f"{type(state).__name__}")
         if hierarchical:

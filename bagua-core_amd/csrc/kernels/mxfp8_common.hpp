@@ -87,4 +87,29 @@ MX_HD void mx8_encode_block(const float (&x)[kMxBlock], float maxf, uint32_t& by
     for (int e = 0; e < kMxBlock; ++e) w[e / 4] |= mx8_quant(mx_clamp(x[e], maxf), inv) << (8 * (e % 4));
 }
 
+// ---- error feedback (MXFP8.md, "Error feedback") -----------------------------------
+// MXFP4's rule (mx_encode_block_ef) with the E4M3 block encode and decode: the compensated
+// value mx_ef_sum and the residual against the decode as T stores it, mx_ef_residual<K>, are
+// mxfp4_common.hpp's.  A decode in T's normal range is exact in T (a 4-bit significand), so
+// mx_as_stored rounds only where MXFP4's does: among the denormals of f16 and bf16.
+// K: 0 f32, 1 f16, 2 bf16.  x[32] as f32 and the residual e[32] -> scale byte, payload words and the new residual
+// (all +0 for a NaN block: the state is reset, not poisoned).
+template <int K>
+MX_HD void mx8_encode_block_ef(const float (&x)[kMxBlock], float (&e)[kMxBlock], float maxf, uint32_t& byte,
+                               uint32_t (&w)[8]) {
+    float v[kMxBlock];
+#pragma unroll
+    for (int i = 0; i < kMxBlock; ++i) v[i] = mx_ef_sum(x[i], e[i]);
+    mx8_encode_block(v, maxf, byte, w);
+    if (byte == kMxNanScale) {
+#pragma unroll
+        for (int i = 0; i < kMxBlock; ++i) e[i] = 0.0f;
+        return;
+    }
+    const float sc = mx8_scale(byte);
+#pragma unroll
+    for (int i = 0; i < kMxBlock; ++i)
+        e[i] = mx_ef_residual<K>(mx_clamp(v[i], maxf), mx8_dequant((w[i / 4] >> (8 * (i % 4))) & 0xffu, sc, maxf));
+}
+
 }  // namespace bagua

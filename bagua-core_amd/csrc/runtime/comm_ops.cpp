@@ -149,7 +149,7 @@ int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_
                    int sched, int average);
 enum { kOpCentralized = 1, kOpCentralizedUnfused, kOpCentralizedPipelined, kOpOneBitPipelined, kOpRing,
        kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback, kOpMxfp4Pipelined, kOpMxfp4Stochastic,
-       kOpMxfp4StochasticPipelined, kOpMxfp8Pipelined };
+       kOpMxfp4StochasticPipelined, kOpMxfp8Pipelined, kOpMxfp8ErrorFeedback };
 
 // The alltoall of the unpieced ops: slot j of recv <- rank j's segment `rank`.  One rank
 // receives its own bytes by a device copy (RCCL's single-rank copy kernel was slower: 1 GiB
@@ -875,22 +875,33 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
     return finish_both(c, BAGUA_OK);
 }
 
-// The MXFP4 op with error feedback (MXFP4.md): centralized()'s steps for the MXFP4 codec
-// with the two `_ef` kernels.  The worker residual compensates what this rank encodes for
-// the alltoall, the server residual the own chunk it re-encodes for the allgather; wire
-// format, collectives, segment sizes and the final decode are the plain op's.  One stream,
-// no pieces; one rank takes the same path (its own bytes arrive by a device copy).
-int centralized_mxfp4_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, float* worker,
-                         float* server) {
+// The MXFP4 / MXFP8 op with error feedback (MXFP4.md, MXFP8.md): centralized()'s steps for
+// the codec with its two `_ef` kernels.  The worker residual compensates what this rank
+// encodes for the alltoall, the server residual the own chunk it re-encodes for the
+// allgather; wire format, collectives, segment sizes and the final decode are the plain op's.
+// One stream, no pieces; one rank takes the same path (its own bytes arrive by a device copy).
+// What differs between the two codecs is the table below.
+struct MxEfCodec {
+    int method, op_kind;
+    decltype(&bagua_mxfp4_compress_ef) compress_ef;
+    decltype(&bagua_mxfp4_reduce_requantize_ef) reduce_requantize_ef;
+};
+const MxEfCodec kMxfp4Ef{BAGUA_COMPRESSION_MXFP4, kOpMxfp4ErrorFeedback, bagua_mxfp4_compress_ef,
+                         bagua_mxfp4_reduce_requantize_ef};
+const MxEfCodec kMxfp8Ef{BAGUA_COMPRESSION_MXFP8, kOpMxfp8ErrorFeedback, bagua_mxfp8_compress_ef,
+                         bagua_mxfp8_reduce_requantize_ef};
+
+int centralized_mx_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, float* worker, float* server,
+                      const MxEfCodec& mx) {
     Chunking k;
-    int rc = plan(c, t, BAGUA_COMPRESSION_MXFP4, &k);
+    int rc = plan(c, t, mx.method, &k);
     if (rc) return rc;
     if (t->ptr % 16)
         return with_aligned_copy(c, {t}, [&](const std::vector<const bagua_tensor_t*>& u) {
-            return centralized_mxfp4_ef(c, u[0], average, worker, server);
+            return centralized_mx_ef(c, u[0], average, worker, server, mx);
         });
     DeviceGuard guard(c->device_id);
-    if ((rc = check_schedule(c, kOpMxfp4ErrorFeedback, BAGUA_COMPRESSION_MXFP4, t, k.cs, 1, average))) return rc;
+    if ((rc = check_schedule(c, mx.op_kind, mx.method, t, k.cs, 1, average))) return rc;
     const uint64_t s = (uint64_t)(uintptr_t)c->stream;
     void* sp = (void*)(uintptr_t)s;
     const int dt = t->dtype, cs = (int)k.cs, p = k.p;
@@ -899,24 +910,42 @@ int centralized_mxfp4_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, i
     TRY(recv.allocate(c->device_id, k.S));
     const bagua_tensor_t sv = u8_view(send.ptr(), k.S, c->device_id);
     // 1. compensate + encode every chunk (worker residual in place)
-    TRY(bagua_mxfp4_compress_ef(dt, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, cs, p, send.as<uint8_t>(), k.S, -1,
-                                worker, sp));
+    TRY(mx.compress_ef(dt, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, cs, p, send.as<uint8_t>(), k.S, -1, worker,
+                       sp));
     // 2. alltoall: slot j of recv <- rank j's segment `rank`
     TRY(alltoall_or_copy(c, k, send.as<void>(), recv.as<void>()));
     // 3. decode the p received versions of the own chunk, reduce, compensate with the server
     // residual, re-encode into send[rank] (the reduced chunk is not stored)
-    rc = bagua_mxfp4_reduce_requantize_ef(dt, recv.as<uint8_t>(), k.S, cs, p, average, send.as<uint8_t>(), k.S, k.rank,
-                                          server, sp);
+    rc = mx.reduce_requantize_ef(dt, recv.as<uint8_t>(), k.S, cs, p, average, send.as<uint8_t>(), k.S, k.rank, server,
+                                 sp);
     if (rc == BAGUA_ERR_UNSUPPORTED)
-        rc = composed_ef_middle(t, BAGUA_COMPRESSION_MXFP4, k, average, recv, send.as<uint8_t>(), s,
+        rc = composed_ef_middle(t, mx.method, k, average, recv, send.as<uint8_t>(), s,
                                 [&](const void* own, uint8_t* seg, size_t co) {
-                                    return bagua_mxfp4_compress_ef(dt, own, cs, cs, 1, seg, co, -1, server, sp);
+                                    return mx.compress_ef(dt, own, cs, cs, 1, seg, co, -1, server, sp);
                                 });
     TRY(rc);
     // 4. allgather the requantised chunks in place, 5. decode everything
     if (p > 1) TRY(bagua_comm_allgather_inplace(c, &sv));
-    TRY(bagua_tensor_decompress_from(t, BAGUA_COMPRESSION_MXFP4, p, &sv, s));
+    TRY(bagua_tensor_decompress_from(t, mx.method, p, &sv, s));
     return finish(c, BAGUA_OK);
+}
+
+// the entry of both: every refusal before anything is launched or posted
+int centralized_mx_ef_entry(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
+                            const bagua_tensor_t* worker_residual, const bagua_tensor_t* server_residual,
+                            const MxEfCodec& mx) {
+    if (!c || !c->t || !t || !t->ptr) return BAGUA_ERR_INVALID_ARG;
+    if (!is_float_dtype(t->dtype)) return BAGUA_ERR_UNSUPPORTED;
+    if (t->num_elem != t->num_elem_allocated) return BAGUA_ERR_UNSUPPORTED;  // partly valid tensors: the plain op only
+    const uint64_t p = c->nranks;
+    if (!t->num_elem || t->num_elem % p || t->num_elem > 0x7fffffffULL || t->device_id != (int)c->device_id)
+        return BAGUA_ERR_INVALID_ARG;
+    float *worker = nullptr, *server = nullptr;
+    int rc;
+    if ((rc = ef_tensor(worker_residual, t->num_elem, t->device_id, &worker)) ||
+        (rc = ef_tensor(server_residual, t->num_elem / p, t->device_id, &server)))
+        return rc;
+    return centralized_mx_ef(c, t, average, worker, server, mx);
 }
 
 // one group of the ring exchange on the side stream
@@ -999,19 +1028,13 @@ int bagua_centralized_onebit_error_feedback(BaguaSingleCommunicatorC* c, const b
 int bagua_centralized_mxfp4_error_feedback(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
                                            const bagua_tensor_t* worker_residual,
                                            const bagua_tensor_t* server_residual) {
-    // every refusal before anything is launched or posted
-    if (!c || !c->t || !t || !t->ptr) return BAGUA_ERR_INVALID_ARG;
-    if (!is_float_dtype(t->dtype)) return BAGUA_ERR_UNSUPPORTED;
-    if (t->num_elem != t->num_elem_allocated) return BAGUA_ERR_UNSUPPORTED;  // partly valid tensors: the plain op only
-    const uint64_t p = c->nranks;
-    if (!t->num_elem || t->num_elem % p || t->num_elem > 0x7fffffffULL || t->device_id != (int)c->device_id)
-        return BAGUA_ERR_INVALID_ARG;
-    float *worker = nullptr, *server = nullptr;
-    int rc;
-    if ((rc = ef_tensor(worker_residual, t->num_elem, t->device_id, &worker)) ||
-        (rc = ef_tensor(server_residual, t->num_elem / p, t->device_id, &server)))
-        return rc;
-    return centralized_mxfp4_ef(c, t, average, worker, server);
+    return centralized_mx_ef_entry(c, t, average, worker_residual, server_residual, kMxfp4Ef);
+}
+
+int bagua_centralized_mxfp8_error_feedback(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
+                                           const bagua_tensor_t* worker_residual,
+                                           const bagua_tensor_t* server_residual) {
+    return centralized_mx_ef_entry(c, t, average, worker_residual, server_residual, kMxfp8Ef);
 }
 
 int bagua_centralized_mxfp4_stochastic(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,

@@ -270,10 +270,12 @@ int bagua_tensor_compress_mxfp4_stochastic(const bagua_tensor_t* t, int n_chunks
     return BAGUA_OK;
 }
 
-// the MXFP4 compress with error-feedback state (bagua_mxfp4_compress_ef): `residual`
-// (num_elem F32) on the tensor's device, 16-B aligned
-int bagua_tensor_compress_mxfp4_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
-                                               const bagua_tensor_t* residual, bagua_tensor_t* out) {
+// the MXFP4 / MXFP8 compress with error-feedback state (bagua_mxfp4_compress_ef /
+// bagua_mxfp8_compress_ef): `residual` (num_elem F32) on the tensor's device, 16-B aligned
+static int compress_mx_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
+                                      const bagua_tensor_t* residual, bagua_tensor_t* out,
+                                      decltype(&bagua_mxfp4_compressed_bytes) compressed_bytes,
+                                      decltype(&bagua_mxfp4_compress_ef) compress_ef) {
     size_t cs = 0;
     int rc = check_chunks(t, n_chunks, &cs);
     if (rc) return rc;
@@ -284,13 +286,12 @@ int bagua_tensor_compress_mxfp4_error_feedback(const bagua_tensor_t* t, int n_ch
         residual->num_elem != t->num_elem || residual->num_elem_allocated != t->num_elem || !residual->ptr ||
         residual->ptr % 16)
         return BAGUA_ERR_INVALID_ARG;
-    const size_t bytes = bagua_mxfp4_compressed_bytes((int)cs, n_chunks);
+    const size_t bytes = compressed_bytes((int)cs, n_chunks);
     if (!bytes) return BAGUA_ERR_UNSUPPORTED;
     uint64_t p = 0;
     if ((rc = pool_alloc(t->device_id, bytes, &p)) != BAGUA_OK) return rc;
-    rc = bagua_mxfp4_compress_ef(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)cs, n_chunks,
-                                 (uint8_t*)(uintptr_t)p, bytes, -1, (float*)(uintptr_t)residual->ptr,
-                                 (void*)(uintptr_t)stream);
+    rc = compress_ef(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)cs, n_chunks,
+                     (uint8_t*)(uintptr_t)p, bytes, -1, (float*)(uintptr_t)residual->ptr, (void*)(uintptr_t)stream);
     if (rc) {
         pool_free(p);
         return rc;
@@ -301,6 +302,18 @@ int bagua_tensor_compress_mxfp4_error_feedback(const bagua_tensor_t* t, int n_ch
     out->dtype = BAGUA_DTYPE_U8;
     out->device_id = t->device_id;
     return BAGUA_OK;
+}
+
+int bagua_tensor_compress_mxfp4_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
+                                               const bagua_tensor_t* residual, bagua_tensor_t* out) {
+    return compress_mx_error_feedback(t, n_chunks, stream, residual, out, bagua_mxfp4_compressed_bytes,
+                                      bagua_mxfp4_compress_ef);
+}
+
+int bagua_tensor_compress_mxfp8_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
+                                               const bagua_tensor_t* residual, bagua_tensor_t* out) {
+    return compress_mx_error_feedback(t, n_chunks, stream, residual, out, bagua_mxfp8_compressed_bytes,
+                                      bagua_mxfp8_compress_ef);
 }
 
 int bagua_tensor_decompress_from(const bagua_tensor_t* t, int method, int n_chunks, const bagua_tensor_t* compressed,

@@ -324,6 +324,23 @@ int bagua_mxfp4_reduce_requantize_ef(int dtype, const uint8_t* input, size_t inp
                                      int num_chunks, int average, uint8_t* output, size_t output_bytes,
                                      int target_chunk, float* residual, bagua_stream_t stream);
 
+/* MXFP8 with error feedback (MXFP8.md, "Error feedback"): MXFP4's rule above with the E4M3
+ * block encode and decode -- the plain MXFP8 wire format, the same f32 state (worker
+ * residual[chunk_size * num_chunks], server residual[chunk_size], zero before the first
+ * step), the same status codes and refusals as their MXFP4 namesakes.  One kernel each, no
+ * workspace.  bagua_mxfp8_compress_ef: target_chunk = -1 only, every chunk fully valid, a
+ * 16-B aligned output.  bagua_mxfp8_reduce_requantize_ef: the residual is checked first, then
+ * what bagua_mxfp8_reduce_requantize checks (16-B aligned input and output); the reduced chunk
+ * is never stored; BAGUA_ERR_UNSUPPORTED for num_chunks > 16: callers then run
+ * bagua_mxfp8_decompress + bagua_reduce_chunks and bagua_mxfp8_compress_ef on the own chunk. */
+int bagua_mxfp8_ef_state_bytes(int chunk_size, int num_chunks, size_t* worker_bytes, size_t* server_bytes);
+int bagua_mxfp8_compress_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                            uint8_t* output, size_t output_bytes, int target_chunk, float* residual,
+                            bagua_stream_t stream);
+int bagua_mxfp8_reduce_requantize_ef(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                     int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                     int target_chunk, float* residual, bagua_stream_t stream);
+
 /* MXFP4 with stochastic rounding (MXFP4.md, "Stochastic rounding"): the plain encode except
  * that an element between two grid values goes to the upper one with probability equal to
  * its fractional position, so the decode's expectation is the input.  No state; wire format,
