@@ -12,6 +12,7 @@ on the communicator's stream:
   CentralizedMXFP4ErrorFeedback        -> bagua_centralized_mxfp4_error_feedback
   CentralizedMXFP4Stochastic           -> bagua_centralized_mxfp4_stochastic
   CentralizedMXFP8ErrorFeedback        -> bagua_centralized_mxfp8_error_feedback
+  CentralizedMXFP8Stochastic           -> bagua_centralized_mxfp8_stochastic
   CentralizedFullPrecisionSynchronous  -> bagua_centralized_full_precision_synchronous
   DecentralizedLowPrecisionSynchronous -> bagua_decentralized_low_precision_synchronous
   PythonOp                             -> a ctypes callback (python_ffi_op.rs)
@@ -31,7 +32,7 @@ from typing import Callable, Optional
 from . import _native as N
 from .communicator import BaguaSingleCommunicatorPy
 from .tensor import (_DTYPES, BaguaTensorPy, MXFP4ErrorFeedbackState, MXFP4StochasticRounding,
-                     MXFP8ErrorFeedbackState, OneBitErrorFeedbackState, compression_code)
+                     MXFP8ErrorFeedbackState, MXFP8StochasticRounding, OneBitErrorFeedbackState, compression_code)
 
 CALLBACK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_char_p)
 
@@ -121,6 +122,26 @@ class CentralizedMXFP8ErrorFeedback:
                                    comm=_handle(self.communicator), ef_worker_carry=st._raw(st.worker_residual),
                                    ef_server_carry=st._raw(st.server_residual))
 
+
+@dataclass
+class CentralizedMXFP8Stochastic:
+    """the "MXFP8" centralized op with stochastic rounding; the native op counts its
+    executions (step 0 is the first after the append)"""
+    communicator: BaguaSingleCommunicatorPy
+    average: bool
+    rounding: MXFP8StochasticRounding
+    compression: str = "MXFP8"
+
+    def native(self) -> N.bagua_bucket_op_t:
+        return N.bagua_bucket_op_sr_t(kind=N.BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC, average=int(self.average),
+                                      compression=compression_code(self.compression), fused=1,
+                                      comm=_handle(self.communicator), sr_seed=self.rounding.seed)
+
+
+# the rounding class of each codec that has stochastic rounding, and the op it appends
+_SR_CODECS = {"MXFP4": (MXFP4StochasticRounding, CentralizedMXFP4Stochastic),
+              "MXFP8": (MXFP8StochasticRounding, CentralizedMXFP8Stochastic)}
+_SR_ROUNDINGS = tuple(r for r, _ in _SR_CODECS.values())
 
 # the state class of each codec that has error feedback, and the op it appends
 _EF_CODECS = {"OneBitSignScale": (OneBitErrorFeedbackState, CentralizedOneBitErrorFeedback),
@@ -255,8 +276,9 @@ class BaguaBucketPy:
         "OneBitSignScale", an MXFP4ErrorFeedbackState with "MXFP4", an MXFP8ErrorFeedbackState
         with "MXFP8".
 
-        stochastic_rounding (keyword; "MXFP4" only, not hierarchical, not together with
-        error_feedback): an MXFP4StochasticRounding.  Both encodes of the op round at random
+        stochastic_rounding (keyword; not hierarchical, not together with error_feedback): an
+        MXFP4StochasticRounding with "MXFP4", an MXFP8StochasticRounding with "MXFP8" (the other
+        codec's rounding is a NotImplementedError).  Both encodes of the op round at random
         with zero bias instead of to nearest; the op's n-th execution uses step n - 1.
         """
         if stochastic_rounding is not None:
@@ -276,20 +298,23 @@ class BaguaBucketPy:
             self._append(CentralizedLowPrecisionSynchronous(comm, average, compression, intranode=intra))
 
     def _append_stochastic(self, comm, hierarchical, average, compression, error_feedback, rounding) -> None:
-        if compression != "MXFP4":
-            raise NotImplementedError(f"stochastic rounding exists for the MXFP4 codec only, not for "
+        if compression not in _SR_CODECS:
+            raise NotImplementedError(f"stochastic rounding exists for the MXFP4 and MXFP8 codecs only, not for "
                                       f"compression={compression!r}")
+        rounding_cls, op_cls = _SR_CODECS[compression]
         if hierarchical:
             raise NotImplementedError("stochastic rounding is not available in hierarchical mode")
         if error_feedback is not None:
             raise NotImplementedError("stochastic rounding and error feedback cannot be combined")
         if comm is None:
             raise RuntimeError("inter node communicator must be given in non-hierarchical mode")
-        if not isinstance(rounding, MXFP4StochasticRounding):
-            raise TypeError("stochastic_rounding must be an MXFP4StochasticRounding")
+        if isinstance(rounding, _SR_ROUNDINGS) and not isinstance(rounding, rounding_cls):
+            raise NotImplementedError(f"{type(rounding).__name__} is not the rounding of compression={compression!r}")
+        if not isinstance(rounding, rounding_cls):
+            raise TypeError(f"stochastic_rounding must be an {rounding_cls.__name__}")
         if self._tensors[0].raw().dtype not in (N.DTYPE_F32, N.DTYPE_F16, N.DTYPE_BF16):
             raise RuntimeError("stochastic rounding needs a floating-point bucket")
-        self._append(CentralizedMXFP4Stochastic(comm, average, rounding))
+        self._append(op_cls(comm, average, rounding))
 
     def _append_error_feedback(self, comm, hierarchical, average, compression, state) -> None:
         if compression not in _EF_CODECS:

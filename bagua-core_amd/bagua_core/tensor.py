@@ -208,21 +208,25 @@ class BaguaTensorPy:
         res._used_on(stream)
         return res
 
-    def compress_with_stochastic_rounding(self, n_chunks: int, rounding: "MXFP4StochasticRounding",
-                                          step: int) -> "BaguaTensorPy":
-        """compress("MXFP4", n_chunks, -1) with every element rounded to one of its two grid
-        neighbours at random, so that the decode's expectation is the input (MXFP4.md,
-        "Stochastic rounding").  The same (rounding.seed, step) gives the same bytes;
-        decompress_from("MXFP4", ...) decodes them.  The result is owned like compress()'s."""
-        if not isinstance(rounding, MXFP4StochasticRounding):
-            raise TypeError("rounding must be an MXFP4StochasticRounding")
+    def compress_with_stochastic_rounding(self, n_chunks: int, rounding, step: int) -> "BaguaTensorPy":
+        """compress("MXFP4" / "MXFP8", n_chunks, -1), the codec being the rounding's (an
+        MXFP4StochasticRounding or an MXFP8StochasticRounding), with every element rounded to
+        one of its two grid neighbours at random, so that the decode's expectation is the input
+        (MXFP4.md, MXFP8.md, "Stochastic rounding").  The same (rounding.seed, step) gives the
+        same bytes; decompress_from of that codec decodes them.  The result is owned like
+        compress()'s."""
+        if isinstance(rounding, MXFP4StochasticRounding):
+            entry = N.C.bagua_tensor_compress_mxfp4_stochastic
+        elif isinstance(rounding, MXFP8StochasticRounding):
+            entry = N.C.bagua_tensor_compress_mxfp8_stochastic
+        else:
+            raise TypeError("rounding must be an MXFP4StochasticRounding or an MXFP8StochasticRounding")
         src = self.raw()
         if n_chunks <= 0 or src.num_elem_allocated % n_chunks != 0:
             raise RuntimeError("compression tensor size % n_chunks must be 0")
         out = N.bagua_tensor_t()
         stream = current_stream_ptr(src.device_id)
-        rc = N.C.bagua_tensor_compress_mxfp4_stochastic(ctypes.byref(src), n_chunks, stream, rounding.seed,
-                                                        int(step) & _U64, ctypes.byref(out))
+        rc = entry(ctypes.byref(src), n_chunks, stream, rounding.seed, int(step) & _U64, ctypes.byref(out))
         N.check(rc, f"compress_with_stochastic_rounding(n_chunks={n_chunks}, step={step})")
         res = BaguaTensorPy._from_raw(out, "compressed_tensor", owned=True)
         res._used_on(stream)
@@ -286,18 +290,25 @@ class BaguaTensorPy:
 _U64 = (1 << 64) - 1
 
 
-class MXFP4StochasticRounding:
-    """Stochastic rounding for the "MXFP4" codec (MXFP4.md): nothing but a seed, taken modulo
-    2^64.  There is no state on the device; an op that takes it counts its own executions, and
-    (seed, step, rank) decide every rounding, so a run is reproducible."""
-
+class _StochasticRounding:
     def __init__(self, seed: int):
         if isinstance(seed, bool) or not isinstance(seed, int):
             raise TypeError("seed must be an int")
         self.seed = seed & _U64
 
     def __repr__(self) -> str:
-        return f"MXFP4StochasticRounding(seed={self.seed:#x})"
+        return f"{type(self).__name__}(seed={self.seed:#x})"
+
+
+class MXFP4StochasticRounding(_StochasticRounding):
+    """Stochastic rounding for the "MXFP4" codec (MXFP4.md): nothing but a seed, taken modulo
+    2^64.  There is no state on the device; an op that takes it counts its own executions, and
+    (seed, step, rank) decide every rounding, so a run is reproducible."""
+
+
+class MXFP8StochasticRounding(_StochasticRounding):
+    """The same for the "MXFP8" codec (MXFP8.md, "Stochastic rounding").  A rounding belongs to
+    its codec: the ops and compress_with_stochastic_rounding tell the two classes apart."""
 
 
 class OneBitErrorFeedbackState:

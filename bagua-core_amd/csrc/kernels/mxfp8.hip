@@ -13,6 +13,10 @@
 //            received versions sixteen elements (one 16-B load) at a time, sums them in the
 //            reference's tree order (reduce.hip), rounds to T and encodes the 32 results
 //
+// SR = true on the encode and the middle step rounds stochastically (MXFP8.md, "Stochastic
+// rounding"): same data movement, mx8_quant_sr or, with HW, one v_cvt_scalef32_sr_fp8_f32 per
+// element.
+//
 // HW = true takes gfx950's conversions (v_cvt_scalef32_pk_fp8_f32 / _pk_f32_fp8) for the
 // rounding to and from E4M3; the scale byte, NaN blocks, magnitude 0x7F, the inf and
 // largest-finite clamps and the rounding to T stay in the arithmetic of mxfp8_common.hpp.
@@ -48,10 +52,18 @@ __device__ __forceinline__ int64_t mx8_valid(int64_t in_num_elem, int64_t cs, in
 // bb is a multiple of kMx8Granule, be another or nb, so a range starts on a wave tile of
 // every kernel and only the range that ends at nb has a ragged tile and the slack.
 // ------------------------------------------------------------------------
-template <typename T, bool HW>
+//
+// SR (MXFP8.md, "Stochastic rounding"): the same kernel with the stochastic element rounding.  A
+// lane hashes once per pair of each of its vectors; the word's index is the pair's index in the
+// whole tensor (chunk * cs + index in chunk), so the bytes do not depend on chunking, range or
+// grid.  A chunk whose base index is odd (guarded path only: such a chunk is never 16-B aligned)
+// takes mx_sr_bits' odd arm, one hash more per vector.  k0 / k1: the halves of the 64-bit key,
+// read by the SR instantiations alone.
+template <typename T, bool HW, bool SR>
 __global__ __launch_bounds__(kBlock) void mxfp8_encode_kernel(const typename T::storage* __restrict__ in,
                                                              int64_t in_num_elem, int64_t cs, int target,
-                                                             uint8_t* __restrict__ out, int64_t bb, int64_t be) {
+                                                             uint8_t* __restrict__ out, int64_t bb, int64_t be,
+                                                             uint32_t k0, uint32_t k1) {
     using S = typename T::storage;
     constexpr int N = Vec<T>::N;           // elements per 16-B vector: 4 / 8
     constexpr int G = kMxBlock / N;        // lanes per block: 8 / 4
@@ -83,7 +95,13 @@ __global__ __launch_bounds__(kBlock) void mxfp8_encode_kernel(const typename T::
             const int64_t b = b0 + k * BW + lb;
             if (b >= nb) continue;
             uint32_t byte, w[N / 4];
-            mx8_encode_lane<N, HW>(f[k], am, maxf, byte, w);
+            if constexpr (SR) {
+                // the lane's vector starts at element sub * N of block bb + b of chunk c
+                const uint32_t j0 = (uint32_t)((int64_t)c * cs + (bb + b) * kMxBlock + sub * N);
+                mx8_encode_lane<N, HW, true>(f[k], am, maxf, byte, w, j0, k0, k1);
+            } else {
+                mx8_encode_lane<N, HW>(f[k], am, maxf, byte, w);
+            }
             mx8_store_lane<N>(seg, pay, b, sub, byte, w, nb, bb, last, sbytes);
         }
     }
@@ -152,12 +170,18 @@ __global__ __launch_bounds__(kBlock) void mxfp8_decode_kernel(const uint8_t* __r
 // reduce them as bagua_reduce_chunks does, round to T and encode the result into the own
 // segment.  Equal, byte for byte, to decompress + bagua_reduce_chunks + compress(target).
 // ------------------------------------------------------------------------
-template <typename T, int BY, bool HW, bool STORE>
+//
+// SR (never storing): the re-encode rounds stochastically, hashing with the index of the own
+// chunk's elements in the whole tensor, j = j_chunk + index with j_chunk = target * cs, as
+// compress_sr(target) does; the decode of the received segments is the plain one.
+template <typename T, int BY, bool HW, bool STORE, bool SR>
 __global__ __launch_bounds__(kBlock) void mxfp8_reduce_encode_kernel(const uint8_t* __restrict__ in, int64_t cs, int p,
                                                                     int average,
                                                                     typename T::storage* __restrict__ chunk,
                                                                     uint8_t* __restrict__ out_seg, int64_t bb,
-                                                                    int64_t be) {
+                                                                    int64_t be, uint32_t j_chunk, uint32_t k0,
+                                                                    uint32_t k1) {
+    static_assert(!(SR && STORE), "the stochastic middle step does not store the reduced chunk");
     constexpr int N = Vec<T>::N;
     const int64_t nb = mx_blocks(cs), sbytes = mx_scale_bytes(cs);
     const int64_t segb = mx8_segment_bytes(cs);
@@ -183,7 +207,8 @@ __global__ __launch_bounds__(kBlock) void mxfp8_reduce_encode_kernel(const uint8
             }
         }
         uint32_t byte, w[8];
-        mx8_encode_whole<HW>(x, maxf, byte, w);
+        if constexpr (SR) mx8_encode_whole<HW, true>(x, maxf, byte, w, j_chunk + (uint32_t)b * kMxBlock, k0, k1);
+        else mx8_encode_whole<HW>(x, maxf, byte, w);
         mx8_store_block(out_seg, pay_out, b, byte, w, nb, sbytes);
     }
 }
@@ -207,7 +232,7 @@ static bool mx8_range(int cs, int& bb, int& be) {
 
 template <typename T>
 static int mx8_compress_impl(const void* input, int in_num_elem, int cs, int p, uint8_t* out, size_t out_bytes,
-                             int target, int bb, int be, hipStream_t s) {
+                             int target, int bb, int be, const uint64_t* key, hipStream_t s) {
     using S = typename T::storage;
     if (!mx_counts_ok(p, cs, kMxGridChunks) || in_num_elem < 0 || target < -1 || target >= p || !out || !input)
         return BAGUA_ERR_INVALID_ARG;
@@ -220,9 +245,13 @@ static int mx8_compress_impl(const void* input, int in_num_elem, int cs, int p, 
     const dim3 grid(mx_grid(((int64_t)(be - bb) + kTileBlocks - 1) / kTileBlocks, kWavesPerBlock, nact,
                             "BAGUA_TUNE_MX8_ENCODE_BLOCKS"),
                     nact);
+    // key: the stochastic encode, under either conversion as the plain one
     with_bool(mx8_hw(), [&](auto hw) {
-        launch(mxfp8_encode_kernel<T, decltype(hw)::value>, grid, dim3(kBlock), 0, s, static_cast<const S*>(input),
-               (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb, (int64_t)be);
+        with_bool(key != nullptr, [&](auto sr) {
+            launch(mxfp8_encode_kernel<T, decltype(hw)::value, decltype(sr)::value>, grid, dim3(kBlock), 0, s,
+                   static_cast<const S*>(input), (int64_t)in_num_elem, (int64_t)cs, target, out, (int64_t)bb,
+                   (int64_t)be, key ? (uint32_t)*key : 0u, key ? (uint32_t)(*key >> 32) : 0u);
+        });
     });
     return check_launch();
 }
@@ -253,7 +282,8 @@ static int mx8_decompress_impl(const uint8_t* in, size_t in_bytes, int cs, int p
 
 template <typename T>
 static int mx8_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, int cs, int p, void* tensor, int average,
-                                      uint8_t* out, size_t out_bytes, int target, int bb, int be, hipStream_t s) {
+                                      uint8_t* out, size_t out_bytes, int target, int bb, int be, const uint64_t* key,
+                                      hipStream_t s) {
     using S = typename T::storage;
     if (!mx_counts_ok(p, cs) || target < 0 || target >= p || !recv || !out) return BAGUA_ERR_INVALID_ARG;
     if (p > kMaxFusedChunks) return BAGUA_ERR_UNSUPPORTED;  // caller runs decompress + reduce + compress
@@ -264,13 +294,19 @@ static int mx8_reduce_requantize_impl(const uint8_t* recv, size_t recv_bytes, in
     S* chunk = tensor ? static_cast<S*>(tensor) + (int64_t)target * cs : nullptr;  // nullptr: not stored
     uint8_t* seg = out + (size_t)target * (size_t)mx8_segment_bytes(cs);
     const int blocks = mx_grid(be - bb, kBlock, 1, "BAGUA_TUNE_MX8_MIDDLE_BLOCKS");
+    const uint32_t jc = key ? (uint32_t)((int64_t)target * cs) : 0u;  // index of the own chunk's first element
     with_by(p, [&](auto by) {
         with_bool(mx8_hw(), [&](auto hw) {
-            with_bool(chunk != nullptr, [&](auto st) {
-                launch(mxfp8_reduce_encode_kernel<T, decltype(by)::value, decltype(hw)::value, decltype(st)::value>,
-                       dim3(blocks), dim3(kBlock), 0, s, recv, (int64_t)cs, p, average, chunk, seg, (int64_t)bb,
-                       (int64_t)be);
-            });
+            constexpr int BY = decltype(by)::value;
+            constexpr bool HW = decltype(hw)::value;
+            auto go = [&](auto kern) {
+                launch(kern, dim3(blocks), dim3(kBlock), 0, s, recv, (int64_t)cs, p, average, chunk, seg, (int64_t)bb,
+                       (int64_t)be, jc, key ? (uint32_t)*key : 0u, key ? (uint32_t)(*key >> 32) : 0u);
+            };
+            // stochastic re-encode (never storing)
+            if (key) go(mxfp8_reduce_encode_kernel<T, BY, HW, false, true>);
+            else if (chunk) go(mxfp8_reduce_encode_kernel<T, BY, HW, true, false>);
+            else go(mxfp8_reduce_encode_kernel<T, BY, HW, false, false>);
         });
     });
     return check_launch();
@@ -289,10 +325,11 @@ size_t bagua_mxfp8_compressed_bytes(int chunk_size, int num_chunks) {
 
 // the whole-chunk entries are the range [0, nb) (kMx8Whole) of the range entries' code
 static int mx8_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
-                        uint8_t* output, size_t output_bytes, int target_chunk, int bb, int be, hipStream_t s) {
+                        uint8_t* output, size_t output_bytes, int target_chunk, int bb, int be, const uint64_t* key,
+                        hipStream_t s) {
     return with_dtype(dtype, [&](auto t) {
         return mx8_compress_impl<decltype(t)>(input, input_num_element, chunk_size, num_chunks, output, output_bytes,
-                                              target_chunk, bb, be, s);
+                                              target_chunk, bb, be, key, s);
     });
 }
 
@@ -305,17 +342,17 @@ static int mx8_decompress(int dtype, const uint8_t* input, size_t input_bytes, i
 
 static int mx8_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
                                  void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
-                                 int bb, int be, hipStream_t s) {
+                                 int bb, int be, const uint64_t* key, hipStream_t s) {
     return with_dtype(dtype, [&](auto t) {
         return mx8_reduce_requantize_impl<decltype(t)>(input, input_bytes, chunk_size, num_chunks, tensor, average,
-                                                       output, output_bytes, target_chunk, bb, be, s);
+                                                       output, output_bytes, target_chunk, bb, be, key, s);
     });
 }
 
 int bagua_mxfp8_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
                          uint8_t* output, size_t output_bytes, int target_chunk, bagua_stream_t stream) {
     return mx8_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, target_chunk,
-                        kMx8Whole, kMx8Whole, static_cast<hipStream_t>(stream));
+                        kMx8Whole, kMx8Whole, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int bagua_mxfp8_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
@@ -328,7 +365,8 @@ int bagua_mxfp8_reduce_requantize(int dtype, const uint8_t* input, size_t input_
                                   void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
                                   bagua_stream_t stream) {
     return mx8_reduce_requantize(dtype, input, input_bytes, chunk_size, num_chunks, tensor, average, output,
-                                 output_bytes, target_chunk, kMx8Whole, kMx8Whole, static_cast<hipStream_t>(stream));
+                                 output_bytes, target_chunk, kMx8Whole, kMx8Whole, nullptr,
+                                 static_cast<hipStream_t>(stream));
 }
 
 // ---- pieces (MXFP8.md, "Pipelined op") ----
@@ -342,7 +380,7 @@ int bagua_mxfp8_compress_range(int dtype, const void* input, int input_num_eleme
                                bagua_stream_t stream) {
     if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
     return mx8_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, -1,
-                        block_begin, block_end, static_cast<hipStream_t>(stream));
+                        block_begin, block_end, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int bagua_mxfp8_decompress_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
@@ -357,7 +395,43 @@ int bagua_mxfp8_reduce_requantize_range(int dtype, const uint8_t* input, size_t 
                                         int target_chunk, int block_begin, int block_end, bagua_stream_t stream) {
     if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
     return mx8_reduce_requantize(dtype, input, input_bytes, chunk_size, num_chunks, nullptr, average, output,
-                                 output_bytes, target_chunk, block_begin, block_end, static_cast<hipStream_t>(stream));
+                                 output_bytes, target_chunk, block_begin, block_end, nullptr,
+                                 static_cast<hipStream_t>(stream));
+}
+
+// ---- stochastic rounding (MXFP8.md, "Stochastic rounding") ----
+// the keys and words are the 4-bit codec's: bagua_mxfp4_sr_key / bagua_mxfp4_sr_word
+int bagua_mxfp8_compress_sr(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                            uint8_t* output, size_t output_bytes, int target_chunk, uint64_t key,
+                            bagua_stream_t stream) {
+    return mx8_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, target_chunk,
+                        kMx8Whole, kMx8Whole, &key, static_cast<hipStream_t>(stream));
+}
+
+int bagua_mxfp8_compress_sr_range(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                                  uint8_t* output, size_t output_bytes, int block_begin, int block_end, uint64_t key,
+                                  bagua_stream_t stream) {
+    if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
+    return mx8_compress(dtype, input, input_num_element, chunk_size, num_chunks, output, output_bytes, -1,
+                        block_begin, block_end, &key, static_cast<hipStream_t>(stream));
+}
+
+int bagua_mxfp8_reduce_requantize_sr(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                     int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                     int target_chunk, uint64_t key, bagua_stream_t stream) {
+    return mx8_reduce_requantize(dtype, input, input_bytes, chunk_size, num_chunks, nullptr, average, output,
+                                 output_bytes, target_chunk, kMx8Whole, kMx8Whole, &key,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int bagua_mxfp8_reduce_requantize_sr_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                           int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                           int target_chunk, int block_begin, int block_end, uint64_t key,
+                                           bagua_stream_t stream) {
+    if (block_begin < 0) return BAGUA_ERR_INVALID_ARG;
+    return mx8_reduce_requantize(dtype, input, input_bytes, chunk_size, num_chunks, nullptr, average, output,
+                                 output_bytes, target_chunk, block_begin, block_end, &key,
+                                 static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

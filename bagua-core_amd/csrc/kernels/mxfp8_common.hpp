@@ -87,6 +87,53 @@ MX_HD void mx8_encode_block(const float (&x)[kMxBlock], float maxf, uint32_t& by
     for (int e = 0; e < kMxBlock; ++e) w[e / 4] |= mx8_quant(mx_clamp(x[e], maxf), inv) << (8 * (e % 4));
 }
 
+// ---- stochastic rounding (MXFP8.md, "Stochastic rounding") ---------------------------
+// The plain block encode with MXFP4's change to the element rounding: 16 bits r of the hash of
+// (key, element index in the tensor) decide between the two neighbouring E4M3 values.  Key,
+// word and r are mxfp4_common.hpp's (mx_sr_key, mx_sr_word, mx_sr_bits), unchanged.
+
+// mx8_quant with the stochastic rule: y = |x * 2^-e| <= 448 lies on the grid of step
+// s = 2^(Ey - 3), Ey = max(floor(log2 y), -6).  Q = floor(y / s * 2^16) (one exact product
+// with the normal power of two 2^(19 - Ey), below 2^20, and a truncating conversion) holds
+// n = floor(y / s) above its 16 fraction bits F, so (Q + r) >> 16 = n + ((F + r) >> 16), and the
+// code of (n + up) * s is n + up + 8 * (Ey + 6) as in mx8_quant.  The largest scaled magnitude
+// is at most 448, a grid value, so the code never passes 0x7E.
+MX_HD uint32_t mx8_quant_sr(float x, float inv, uint32_t r) {
+    const float y = x * inv;
+    const uint32_t yb = mx_bits(y), ya = yb & 0x7fffffffu;
+    const uint32_t me = (ya > 0x3c800000u ? ya : 0x3c800000u) & 0x7f800000u;
+    const uint32_t q = (uint32_t)(mx_float(ya) * mx_float(0x88800000u - me));
+    return (((q + r) >> 16) + (me >> 20) - 968u) | ((yb >> 24) & 0x80u);
+}
+
+// mx8_encode_block under the stochastic rule; j0: the index of x[0] in the whole tensor
+MX_HD void mx8_encode_block_sr(const float (&x)[kMxBlock], float maxf, uint32_t j0, uint32_t k0, uint32_t k1,
+                               uint32_t& byte, uint32_t (&w)[8]) {
+    uint32_t am = 0;
+#pragma unroll
+    for (int e = 0; e < kMxBlock; ++e) {
+        const uint32_t a = mx_bits(x[e]) & 0x7fffffffu;
+        am = a > am ? a : am;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] = 0u;
+    if (am > 0x7f800000u) {  // a NaN in the block
+        byte = kMxNanScale;
+        return;
+    }
+    const uint32_t mb = mx_bits(maxf);
+    byte = mx8_scale_byte(am < mb ? am : mb);
+    const float inv = mx8_inv_scale(byte);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t r[8];
+        mx_sr_bits<8>(j0 + 8u * k, k0, k1, r);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            w[2 * k + e / 4] |= mx8_quant_sr(mx_clamp(x[8 * k + e], maxf), inv, r[e]) << (8 * (e % 4));
+    }
+}
+
 // ---- error feedback (MXFP8.md, "Error feedback") -----------------------------------
 // MXFP4's rule (mx_encode_block_ef) with the E4M3 block encode and decode: the compensated
 // value mx_ef_sum and the residual against the decode as T stores it, mx_ef_residual<K>, are

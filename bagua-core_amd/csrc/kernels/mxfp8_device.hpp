@@ -68,9 +68,42 @@ __device__ __forceinline__ void mx8_decode(const uint32_t (&w)[NB / 4], uint32_t
 // the N (a multiple of 4) payload bytes of N values (f32, not yet clamped) of a block without
 // NaN under the block's scale byte, element e in byte e % 4 of word e / 4.  HW: gfx950's
 // v_cvt_scalef32_pk_fp8_f32, two elements into one half of the word per instruction.
-template <int N, bool HW>
-__device__ __forceinline__ void mx8_quant_lane(const float* f, uint32_t byte, float maxf, uint32_t (&w)[N / 4]) {
-    if constexpr (HW) {
+// SR (MXFP8.md, "Stochastic rounding"): j0 is the index of f[0] in the whole tensor, k0 / k1 the
+// halves of the key (unused otherwise); one hash per pair of elements, then mx8_quant_sr, or
+// with HW one v_cvt_scalef32_sr_fp8_f32 per element into its byte of the word, its 32-bit
+// seed holding the element's r in the upper half.
+template <int N, bool HW, bool SR = false>
+__device__ __forceinline__ void mx8_quant_lane(const float* f, uint32_t byte, float maxf, uint32_t (&w)[N / 4],
+                                               uint32_t j0 = 0, uint32_t k0 = 0, uint32_t k1 = 0) {
+    if constexpr (SR) {
+        uint32_t r[N];
+        mx_sr_bits<N>(j0, k0, k1, r);
+        if constexpr (HW) {
+            // seed = r << 16: f32 has 20 bits below an E4M3 step and the contract's F is their top 16.
+            // That covers normal results; that subnormal results and scale bytes 0 and 1 give the
+            // contract's bytes too is established on the GPU by test_boundary_table
+            // (tests/test_gpu_mxfp8_sr.py), not by the argument.
+            const float scale = __uint_as_float(byte << 23);
+#pragma unroll
+            for (int k = 0; k < N / 4; ++k) {
+                int v = 0;
+                v = __builtin_amdgcn_cvt_scalef32_sr_fp8_f32(v, mx_clamp(f[4 * k], maxf), r[4 * k] << 16, scale, 0);
+                v = __builtin_amdgcn_cvt_scalef32_sr_fp8_f32(v, mx_clamp(f[4 * k + 1], maxf), r[4 * k + 1] << 16, scale, 1);
+                v = __builtin_amdgcn_cvt_scalef32_sr_fp8_f32(v, mx_clamp(f[4 * k + 2], maxf), r[4 * k + 2] << 16, scale, 2);
+                v = __builtin_amdgcn_cvt_scalef32_sr_fp8_f32(v, mx_clamp(f[4 * k + 3], maxf), r[4 * k + 3] << 16, scale, 3);
+                w[k] = (uint32_t)v;
+            }
+        } else {
+            const float inv = mx8_inv_scale(byte);
+#pragma unroll
+            for (int k = 0; k < N / 4; ++k) {
+                w[k] = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    w[k] |= mx8_quant_sr(mx_clamp(f[4 * k + e], maxf), inv, r[4 * k + e]) << (8 * e);
+            }
+        }
+    } else if constexpr (HW) {
         const float scale = __uint_as_float(byte << 23);
 #pragma unroll
         for (int k = 0; k < N / 4; ++k) {
@@ -93,30 +126,34 @@ __device__ __forceinline__ void mx8_quant_lane(const float* f, uint32_t byte, fl
 }
 
 // The lane's part of a cooperative block encode after mx_block_amax: from the block's amax its
-// scale byte and the lane's payload words; a NaN block: 0xFF and zero words.
-template <int N, bool HW>
+// scale byte and the lane's payload words; a NaN block: 0xFF and zero words.  j0, k0, k1: as
+// mx8_quant_lane's.
+template <int N, bool HW, bool SR = false>
 __device__ __forceinline__ void mx8_encode_lane(const float (&f)[N], uint32_t am, float maxf, uint32_t& byte,
-                                                uint32_t (&w)[N / 4]) {
+                                                uint32_t (&w)[N / 4], uint32_t j0 = 0, uint32_t k0 = 0,
+                                                uint32_t k1 = 0) {
     byte = kMxNanScale;
 #pragma unroll
     for (int k = 0; k < N / 4; ++k) w[k] = 0;
     if (am <= 0x7f800000u) {
         byte = mx8_scale_byte(min(am, __float_as_uint(maxf)));
-        mx8_quant_lane<N, HW>(f, byte, maxf, w);
+        mx8_quant_lane<N, HW, SR>(f, byte, maxf, w, j0, k0, k1);
     }
 }
 
-// scale byte and payload words of one whole block held by one lane (x: f32, invalid elements +0)
-template <bool HW>
+// scale byte and payload words of one whole block held by one lane (x: f32, invalid elements +0);
+// SR: x[0] is element j0 of the whole tensor
+template <bool HW, bool SR = false>
 __device__ __forceinline__ void mx8_encode_whole(const float (&x)[kMxBlock], float maxf, uint32_t& byte,
-                                                 uint32_t (&w)[8]) {
+                                                 uint32_t (&w)[8], uint32_t j0 = 0, uint32_t k0 = 0, uint32_t k1 = 0) {
     if constexpr (!HW) {
-        mx8_encode_block(x, maxf, byte, w);
+        if constexpr (SR) mx8_encode_block_sr(x, maxf, j0, k0, k1, byte, w);
+        else mx8_encode_block(x, maxf, byte, w);
     } else {
         uint32_t am = 0;
 #pragma unroll
         for (int e = 0; e < kMxBlock; ++e) am = max(am, __float_as_uint(x[e]) & 0x7fffffffu);
-        mx8_encode_lane<kMxBlock, true>(x, am, maxf, byte, w);
+        mx8_encode_lane<kMxBlock, true, SR>(x, am, maxf, byte, w, j0, k0, k1);
     }
 }
 

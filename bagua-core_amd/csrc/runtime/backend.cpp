@@ -176,6 +176,8 @@ int run_op(BaguaBucketC* b, size_t index, const bagua_bucket_op_t& op, const bag
                                                           &op.ef_server_carry);
         case BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC:
             return bagua_centralized_mxfp4_stochastic(op.comm, flat, op.average, op.sr_seed, b->next_step(index), 0);
+        case BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC:
+            return bagua_centralized_mxfp8_stochastic(op.comm, flat, op.average, op.sr_seed, b->next_step(index), 0);
         case BAGUA_BUCKET_OP_CALLBACK:
             // the callback sees the previous ops' results, as in the reference (their
             // Drop synced), also when the worker runs the ops async
@@ -639,17 +641,19 @@ int bagua_bucket_append_op(BaguaBucketC* b, const bagua_bucket_op_t* op) {
     if (op->kind != BAGUA_BUCKET_OP_CALLBACK && !op->comm && !op->intranode) return BAGUA_ERR_INVALID_ARG;
     if (op->intranode && op->intranode->rank == 0 && !op->comm) return BAGUA_ERR_INVALID_ARG;
     if (op->kind < BAGUA_BUCKET_OP_CENTRALIZED_LOW_PRECISION ||
-        op->kind > BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK)
+        op->kind > BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC)
         return BAGUA_ERR_UNSUPPORTED;
-    // sr_seed was appended for the stochastic op: the older kinds are read up to it only, so
+    // sr_seed was appended for the stochastic ops: the other kinds are read up to it only, so
     // callers built against the shorter struct stay valid for them
+    const bool stochastic = op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC ||
+                            op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC;
     bagua_bucket_op_t copy{};
-    std::memcpy(&copy, op,
-                op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC ? sizeof(copy)
-                                                                         : offsetof(bagua_bucket_op_t, sr_seed));
-    if (op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC) {
-        // MXFP4 codec only, no hierarchical mode, no error-feedback state beside it
-        if (op->intranode || op->compression != BAGUA_COMPRESSION_MXFP4) return BAGUA_ERR_UNSUPPORTED;
+    std::memcpy(&copy, op, stochastic ? sizeof(copy) : offsetof(bagua_bucket_op_t, sr_seed));
+    if (stochastic) {
+        // the kind's own codec only, no hierarchical mode, no error-feedback state beside it
+        const int codec = op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC ? BAGUA_COMPRESSION_MXFP4
+                                                                                   : BAGUA_COMPRESSION_MXFP8;
+        if (op->intranode || op->compression != codec) return BAGUA_ERR_UNSUPPORTED;
         if (op->ef_worker_carry.ptr || op->ef_worker_scales.ptr || op->ef_server_carry.ptr || op->ef_server_scale.ptr)
             return BAGUA_ERR_INVALID_ARG;
     }

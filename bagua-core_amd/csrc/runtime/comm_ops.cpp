@@ -149,7 +149,8 @@ int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_
                    int sched, int average);
 enum { kOpCentralized = 1, kOpCentralizedUnfused, kOpCentralizedPipelined, kOpOneBitPipelined, kOpRing,
        kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback, kOpMxfp4Pipelined, kOpMxfp4Stochastic,
-       kOpMxfp4StochasticPipelined, kOpMxfp8Pipelined, kOpMxfp8ErrorFeedback };
+       kOpMxfp4StochasticPipelined, kOpMxfp8Pipelined, kOpMxfp8ErrorFeedback, kOpMxfp8Stochastic,
+       kOpMxfp8StochasticPipelined };
 
 // The alltoall of the unpieced ops: slot j of recv <- rank j's segment `rank`.  One rank
 // receives its own bytes by a device copy (RCCL's single-rank copy kernel was slower: 1 GiB
@@ -175,22 +176,69 @@ int composed_ef_middle(const bagua_tensor_t* t, int method, const Chunking& k, i
                        sb + (size_t)k.rank * co, co);
 }
 
-// The keys of one execution of the MXFP4 op with stochastic rounding (MXFP4.md): stage 0,
-// this rank's encode of every chunk, and stage 1, its re-encode of the reduced own chunk.
+// The keys of one execution of a block codec's op with stochastic rounding (MXFP4.md,
+// MXFP8.md): stage 0, this rank's encode of every chunk, and stage 1, its re-encode of the
+// reduced own chunk.
 struct MxSrKeys {
     uint64_t worker, server;
 };
 
-// bagua_tensor_compress_into for the MXFP4 codec under a key; cs fits an int (plan, below)
-int mxfp4_compress_keyed(const bagua_tensor_t* t, const Chunking& k, int target, uint64_t key, const bagua_tensor_t& out,
-                         uint64_t stream) {
-    if (k.cs > 0x7fffffffULL || t->num_elem > 0x7fffffffULL) return BAGUA_ERR_INVALID_ARG;
-    return bagua_mxfp4_compress_sr(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)k.cs, k.p,
-                                   (uint8_t*)(uintptr_t)out.ptr, k.S, target, key, (void*)(uintptr_t)stream);
+// What differs between the two block codecs in centralized() and in the pipelined schedule
+// (MXFP8.md, "Pipelined op"): the entries of the middle step and of the keyed encodes, the
+// three range entries with their keyed forms, the piece table and the op kinds of the plain
+// pipelined op and of the stochastic op, unpieced and pieced.
+struct MxCodec {
+    int method, op_kind, sr_kind, sr_pieced_kind;
+    decltype(&bagua_mxfp4_compress_range) compress_range;
+    decltype(&bagua_mxfp4_reduce_requantize_range) reduce_requantize_range;
+    decltype(&bagua_mxfp4_decompress_range) decompress_range;
+    decltype(&mxfp4_pieces) pieces;
+    decltype(&bagua_mxfp4_reduce_requantize) reduce_requantize;
+    decltype(&bagua_mxfp4_compress_sr) compress_sr;
+    decltype(&bagua_mxfp4_reduce_requantize_sr) reduce_requantize_sr;
+    decltype(&bagua_mxfp4_compress_sr_range) compress_sr_range;
+    decltype(&bagua_mxfp4_reduce_requantize_sr_range) reduce_requantize_sr_range;
+};
+const MxCodec kMxfp4{BAGUA_COMPRESSION_MXFP4,
+                     kOpMxfp4Pipelined,
+                     kOpMxfp4Stochastic,
+                     kOpMxfp4StochasticPipelined,
+                     bagua_mxfp4_compress_range,
+                     bagua_mxfp4_reduce_requantize_range,
+                     bagua_mxfp4_decompress_range,
+                     mxfp4_pieces,
+                     bagua_mxfp4_reduce_requantize,
+                     bagua_mxfp4_compress_sr,
+                     bagua_mxfp4_reduce_requantize_sr,
+                     bagua_mxfp4_compress_sr_range,
+                     bagua_mxfp4_reduce_requantize_sr_range};
+const MxCodec kMxfp8{BAGUA_COMPRESSION_MXFP8,
+                     kOpMxfp8Pipelined,
+                     kOpMxfp8Stochastic,
+                     kOpMxfp8StochasticPipelined,
+                     bagua_mxfp8_compress_range,
+                     bagua_mxfp8_reduce_requantize_range,
+                     bagua_mxfp8_decompress_range,
+                     mxfp8_pieces,
+                     bagua_mxfp8_reduce_requantize,
+                     bagua_mxfp8_compress_sr,
+                     bagua_mxfp8_reduce_requantize_sr,
+                     bagua_mxfp8_compress_sr_range,
+                     bagua_mxfp8_reduce_requantize_sr_range};
+const MxCodec* mx_codec(int method) {
+    return method == BAGUA_COMPRESSION_MXFP4 ? &kMxfp4 : method == BAGUA_COMPRESSION_MXFP8 ? &kMxfp8 : nullptr;
 }
 
-// sr (MXFP4 only): both encodes round stochastically under its keys; every other step,
-// buffer and collective is the plain op's
+// bagua_tensor_compress_into for a block codec under a key; cs fits an int (plan, below)
+int mx_compress_keyed(const MxCodec& mx, const bagua_tensor_t* t, const Chunking& k, int target, uint64_t key,
+                      const bagua_tensor_t& out, uint64_t stream) {
+    if (k.cs > 0x7fffffffULL || t->num_elem > 0x7fffffffULL) return BAGUA_ERR_INVALID_ARG;
+    return mx.compress_sr(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)k.cs, k.p,
+                          (uint8_t*)(uintptr_t)out.ptr, k.S, target, key, (void*)(uintptr_t)stream);
+}
+
+// sr (the block codecs only): both encodes round stochastically under its keys; every other
+// step, buffer and collective is the plain op's
 int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int method, bool fused,
                 const MxSrKeys* sr = nullptr) {
     OpTimer tm;
@@ -209,8 +257,10 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
     int rc = plan(c, t, method, &k);
     if (rc) return rc;
     DeviceGuard guard(c->device_id);
-    if ((rc = check_schedule(c, sr ? kOpMxfp4Stochastic : fused ? kOpCentralized : kOpCentralizedUnfused, method, t,
-                             k.cs, 1, average)))
+    const MxCodec* const mx = mx_codec(method);
+    if (sr && !mx) return BAGUA_ERR_UNSUPPORTED;
+    if ((rc = check_schedule(c, sr ? mx->sr_kind : fused ? kOpCentralized : kOpCentralizedUnfused, method, t, k.cs, 1,
+                             average)))
         return rc;
     const uint64_t s = (uint64_t)(uintptr_t)c->stream;
     if (k.p == 1 && fused && method == BAGUA_COMPRESSION_MINMAX_UINT8 && t->num_elem == t->num_elem_allocated &&
@@ -252,7 +302,7 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
     const bagua_tensor_t rv = u8_view(recv.ptr(), k.S, c->device_id);
     ph[0] = tm.lap();
     // 1. compress every chunk (target -1)
-    if (sr) TRY(mxfp4_compress_keyed(t, k, -1, sr->worker, sv, s));
+    if (sr) TRY(mx_compress_keyed(*mx, t, k, -1, sr->worker, sv, s));
     else TRY(bagua_tensor_compress_into(t, method, k.p, s, -1, &sv));
     ph[1] = tm.lap();
     if (!self_alias) TRY(alltoall_or_copy(c, k, send.as<void>(), recv.as<void>()));
@@ -303,25 +353,19 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
                                             (void*)(uintptr_t)ws, ws_bytes, (void*)(uintptr_t)s);
         if (rc == BAGUA_OK) done = true;
         else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
-    } else if (fused && method == BAGUA_COMPRESSION_MXFP4 && t->num_elem == t->num_elem_allocated) {
-        // one kernel, no workspace; the reduced chunk is not stored (step 5 rewrites every element)
-        rc = sr ? bagua_mxfp4_reduce_requantize_sr(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, average,
-                                                   send.as<uint8_t>(), k.S, k.rank, sr->server, (void*)(uintptr_t)s)
-                : bagua_mxfp4_reduce_requantize(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, nullptr, average,
-                                                send.as<uint8_t>(), k.S, k.rank, (void*)(uintptr_t)s);
-        if (rc == BAGUA_OK) done = true;
-        else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
-    } else if (fused && method == BAGUA_COMPRESSION_MXFP8 && t->num_elem == t->num_elem_allocated) {
-        // likewise (MXFP8.md)
-        rc = bagua_mxfp8_reduce_requantize(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, nullptr, average,
-                                           send.as<uint8_t>(), k.S, k.rank, (void*)(uintptr_t)s);
+    } else if (fused && mx && t->num_elem == t->num_elem_allocated) {
+        // MXFP4 / MXFP8: one kernel, no workspace; the reduced chunk is not stored (step 5 rewrites every element)
+        rc = sr ? mx->reduce_requantize_sr(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, average,
+                                           send.as<uint8_t>(), k.S, k.rank, sr->server, (void*)(uintptr_t)s)
+                : mx->reduce_requantize(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, nullptr, average,
+                                        send.as<uint8_t>(), k.S, k.rank, (void*)(uintptr_t)s);
         if (rc == BAGUA_OK) done = true;
         else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
     }
     if (!done) {
         TRY(bagua_tensor_decompress_from(t, method, k.p, rview, s));
         TRY(bagua_tensor_reduce_inplace(t, k.p, k.rank, average, s));
-        if (sr) TRY(mxfp4_compress_keyed(t, k, k.rank, sr->server, sv, s));
+        if (sr) TRY(mx_compress_keyed(*mx, t, k, k.rank, sr->server, sv, s));
         else TRY(bagua_tensor_compress_into(t, method, k.p, s, k.rank, &sv));
     }
     // 4. allgather the requantised chunks in place (one rank: nothing to move), 5. decompress everything
@@ -787,31 +831,16 @@ int centralized_onebit_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, 
 //    the own chunk, G its allgather, D decode piece q of all chunks; M_q waits for A_q
 //    only, G_q for M_q, D_q for G_q; the side stream posts A0 .. Ak, then G0 .. Gk)
 //
-// sr: the same schedule with both encodes stochastic (MXFP4.md, "Stochastic rounding").  A
-// word depends on the key and the element's index alone, so every piece count gives the
-// unpieced op's bytes.
+// sr: the same schedule with both encodes stochastic (MXFP4.md, MXFP8.md, "Stochastic
+// rounding").  A word depends on the key and the element's index alone, so every piece count
+// gives the unpieced op's bytes.
 //
-// The schedule serves both block codecs (MXFP8.md, "Pipelined op"): what differs is the three
-// range entries, the piece table and the op kind.  sr: kMxfp4 only.
-struct MxCodec {
-    int method, op_kind;
-    decltype(&bagua_mxfp4_compress_range) compress_range;
-    decltype(&bagua_mxfp4_reduce_requantize_range) reduce_requantize_range;
-    decltype(&bagua_mxfp4_decompress_range) decompress_range;
-    decltype(&mxfp4_pieces) pieces;
-};
-const MxCodec kMxfp4{BAGUA_COMPRESSION_MXFP4,           kOpMxfp4Pipelined,
-                     bagua_mxfp4_compress_range,        bagua_mxfp4_reduce_requantize_range,
-                     bagua_mxfp4_decompress_range,      mxfp4_pieces};
-const MxCodec kMxfp8{BAGUA_COMPRESSION_MXFP8,           kOpMxfp8Pipelined,
-                     bagua_mxfp8_compress_range,        bagua_mxfp8_reduce_requantize_range,
-                     bagua_mxfp8_decompress_range,      mxfp8_pieces};
+// The schedule serves both block codecs through their MxCodec table (above).
 
-int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int pieces,
-                                const MxSrKeys* sr = nullptr, const MxCodec& mx = kMxfp4) {
+int centralized_pipelined_mx(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, int pieces,
+                             const MxCodec& mx, const MxSrKeys* sr = nullptr) {
     Chunking k;
     if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
-    if (sr && mx.method != BAGUA_COMPRESSION_MXFP4) return BAGUA_ERR_UNSUPPORTED;  // the keyed kernels are MXFP4's
     int rc = plan(c, t, mx.method, &k);
     if (rc) return rc;
     const int caller = pieces;
@@ -824,11 +853,11 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
         return centralized(c, t, average, mx.method, true, sr);
     if (t->ptr % 16)  // this rank alone: the same schedule on an aligned staging copy
         return with_aligned_copy(c, {t}, [&](const std::vector<const bagua_tensor_t*>& u) {
-            return centralized_pipelined_mxfp4(c, u[0], average, caller, sr, mx);
+            return centralized_pipelined_mx(c, u[0], average, caller, mx, sr);
         });
     const int sched = op_schedule(c->cfg, pieces, caller);
     DeviceGuard guard(c->device_id);
-    if ((rc = check_schedule(c, sr ? kOpMxfp4StochasticPipelined : mx.op_kind, mx.method, t, k.cs, sched, average)))
+    if ((rc = check_schedule(c, sr ? mx.sr_pieced_kind : mx.op_kind, mx.method, t, k.cs, sched, average)))
         return rc;
     if (c->ensure_side(4 * (size_t)pieces + 1)) return finish(c, BAGUA_ERR_HIP);
     hipStream_t s0 = c->stream;
@@ -850,8 +879,7 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
     // events are recorded all the same)
     for (int q = 0; q < pieces; ++q) {
         if (tab[q].b < tab[q].e)
-            TRY2(sr ? bagua_mxfp4_compress_sr_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, tab[q].b, tab[q].e,
-                                                    sr->worker, s0)
+            TRY2(sr ? mx.compress_sr_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, tab[q].b, tab[q].e, sr->worker, s0)
                     : mx.compress_range(dt, x, (int)t->num_elem, cs, p, sb, k.S, tab[q].b, tab[q].e, s0));
         HIP2(hipEventRecord(encoded[q], s0));
     }
@@ -861,8 +889,8 @@ int centralized_pipelined_mxfp4(BaguaSingleCommunicatorC* c, const bagua_tensor_
     for (int q = 0; q < pieces; ++q) {
         HIP2(hipStreamWaitEvent(s0, exchanged[q], 0));
         if (tab[q].b < tab[q].e)
-            TRY2(sr ? bagua_mxfp4_reduce_requantize_sr_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, tab[q].b,
-                                                             tab[q].e, sr->server, s0)
+            TRY2(sr ? mx.reduce_requantize_sr_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, tab[q].b, tab[q].e,
+                                                    sr->server, s0)
                     : mx.reduce_requantize_range(dt, rb, k.S, cs, p, average, sb, k.S, k.rank, tab[q].b, tab[q].e, s0));
         HIP2(hipEventRecord(requantised[q], s0));
     }
@@ -996,8 +1024,8 @@ extern "C" {
 int bagua_centralized_low_precision_pipelined(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
                                               int method, int pieces) {
     if (method == BAGUA_COMPRESSION_ONEBIT) return centralized_pipelined_onebit(c, t, average, pieces);
-    if (method == BAGUA_COMPRESSION_MXFP4) return centralized_pipelined_mxfp4(c, t, average, pieces);
-    if (method == BAGUA_COMPRESSION_MXFP8) return centralized_pipelined_mxfp4(c, t, average, pieces, nullptr, kMxfp8);
+    if (method == BAGUA_COMPRESSION_MXFP4) return centralized_pipelined_mx(c, t, average, pieces, kMxfp4);
+    if (method == BAGUA_COMPRESSION_MXFP8) return centralized_pipelined_mx(c, t, average, pieces, kMxfp8);
     if (method != BAGUA_COMPRESSION_MINMAX_UINT8) return centralized(c, t, average, method, true);
     return centralized_pipelined(c, t, average, pieces);
 }
@@ -1037,15 +1065,26 @@ int bagua_centralized_mxfp8_error_feedback(BaguaSingleCommunicatorC* c, const ba
     return centralized_mx_ef_entry(c, t, average, worker_residual, server_residual, kMxfp8Ef);
 }
 
-int bagua_centralized_mxfp4_stochastic(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
-                                       uint64_t seed, uint64_t step, int pieces) {
+// the stochastic op of either block codec
+static int centralized_mx_stochastic(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, uint64_t seed,
+                                     uint64_t step, int pieces, const MxCodec& mx) {
     // every refusal before anything is launched or posted
     if (!c || !c->t || !t || !t->ptr) return BAGUA_ERR_INVALID_ARG;
     if (!valid_schedule(pieces)) return BAGUA_ERR_INVALID_ARG;
     if (!is_float_dtype(t->dtype)) return BAGUA_ERR_UNSUPPORTED;
     // the keys are this rank's alone: no byte count and no collective depends on them
     const MxSrKeys sr{bagua_mxfp4_sr_key(seed, step, (int)c->rank, 0), bagua_mxfp4_sr_key(seed, step, (int)c->rank, 1)};
-    return centralized_pipelined_mxfp4(c, t, average, pieces, &sr);
+    return centralized_pipelined_mx(c, t, average, pieces, mx, &sr);
+}
+
+int bagua_centralized_mxfp4_stochastic(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
+                                       uint64_t seed, uint64_t step, int pieces) {
+    return centralized_mx_stochastic(c, t, average, seed, step, pieces, kMxfp4);
+}
+
+int bagua_centralized_mxfp8_stochastic(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
+                                       uint64_t seed, uint64_t step, int pieces) {
+    return centralized_mx_stochastic(c, t, average, seed, step, pieces, kMxfp8);
 }
 
 int bagua_centralized_low_precision_synchronous(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,

@@ -243,21 +243,22 @@ int bagua_tensor_compress_error_feedback(const bagua_tensor_t* t, int n_chunks, 
     return BAGUA_OK;
 }
 
-// the MXFP4 compress with stochastic rounding (bagua_mxfp4_compress_sr), rank 0 and stage 0
-int bagua_tensor_compress_mxfp4_stochastic(const bagua_tensor_t* t, int n_chunks, uint64_t stream, uint64_t seed,
-                                           uint64_t step, bagua_tensor_t* out) {
+// the MXFP4 / MXFP8 compress with stochastic rounding (bagua_mxfp4_compress_sr /
+// bagua_mxfp8_compress_sr) under the key of rank 0 and stage 0
+static int compress_mx_stochastic(const bagua_tensor_t* t, int n_chunks, uint64_t stream, uint64_t seed, uint64_t step,
+                                  bagua_tensor_t* out, decltype(&bagua_mxfp4_compressed_bytes) compressed_bytes,
+                                  decltype(&bagua_mxfp4_compress_sr) compress_sr) {
     size_t cs = 0;
     int rc = check_chunks(t, n_chunks, &cs);
     if (rc) return rc;
     if (!out) return BAGUA_ERR_INVALID_ARG;
     if (!codec_dtype(t->dtype)) return BAGUA_ERR_UNSUPPORTED;
-    const size_t bytes = bagua_mxfp4_compressed_bytes((int)cs, n_chunks);
+    const size_t bytes = compressed_bytes((int)cs, n_chunks);
     if (!bytes) return BAGUA_ERR_UNSUPPORTED;
     uint64_t p = 0;
     if ((rc = pool_alloc(t->device_id, bytes, &p)) != BAGUA_OK) return rc;
-    rc = bagua_mxfp4_compress_sr(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)cs, n_chunks,
-                                 (uint8_t*)(uintptr_t)p, bytes, -1, bagua_mxfp4_sr_key(seed, step, 0, 0),
-                                 (void*)(uintptr_t)stream);
+    rc = compress_sr(t->dtype, (const void*)(uintptr_t)t->ptr, (int)t->num_elem, (int)cs, n_chunks,
+                     (uint8_t*)(uintptr_t)p, bytes, -1, bagua_mxfp4_sr_key(seed, step, 0, 0), (void*)(uintptr_t)stream);
     if (rc) {
         pool_free(p);
         return rc;
@@ -268,6 +269,18 @@ int bagua_tensor_compress_mxfp4_stochastic(const bagua_tensor_t* t, int n_chunks
     out->dtype = BAGUA_DTYPE_U8;
     out->device_id = t->device_id;
     return BAGUA_OK;
+}
+
+int bagua_tensor_compress_mxfp4_stochastic(const bagua_tensor_t* t, int n_chunks, uint64_t stream, uint64_t seed,
+                                           uint64_t step, bagua_tensor_t* out) {
+    return compress_mx_stochastic(t, n_chunks, stream, seed, step, out, bagua_mxfp4_compressed_bytes,
+                                  bagua_mxfp4_compress_sr);
+}
+
+int bagua_tensor_compress_mxfp8_stochastic(const bagua_tensor_t* t, int n_chunks, uint64_t stream, uint64_t seed,
+                                           uint64_t step, bagua_tensor_t* out) {
+    return compress_mx_stochastic(t, n_chunks, stream, seed, step, out, bagua_mxfp8_compressed_bytes,
+                                  bagua_mxfp8_compress_sr);
 }
 
 // the MXFP4 / MXFP8 compress with error-feedback state (bagua_mxfp4_compress_ef /

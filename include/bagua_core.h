@@ -109,6 +109,9 @@ int bagua_tensor_compress_mxfp8_error_feedback(const bagua_tensor_t* t, int n_ch
  * bagua_mxfp4_sr_key(seed, step, 0, 0); bagua_tensor_decompress_from decodes it. */
 int bagua_tensor_compress_mxfp4_stochastic(const bagua_tensor_t* t, int n_chunks, uint64_t stream, uint64_t seed,
                                            uint64_t step, bagua_tensor_t* out);
+/* the same with the "MXFP8" codec (bagua_mxfp8_compress_sr; MXFP8.md, "Stochastic rounding") */
+int bagua_tensor_compress_mxfp8_stochastic(const bagua_tensor_t* t, int n_chunks, uint64_t stream, uint64_t seed,
+                                           uint64_t step, bagua_tensor_t* out);
 /* RawBaguaTensor::decompress_from (datatypes/mod.rs:398-446) */
 int bagua_tensor_decompress_from(const bagua_tensor_t* t, int method, int n_chunks,
                                  const bagua_tensor_t* compressed, uint64_t stream);
@@ -191,6 +194,10 @@ int bagua_comm_set_async(BaguaSingleCommunicatorC* comm, int on);
  * gives the same bytes.  Seeds and steps need not agree across ranks.  There is no
  * hierarchical form. */
 int bagua_centralized_mxfp4_stochastic(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t, int average,
+                                       uint64_t seed, uint64_t step, int pieces);
+/* The same op with the MXFP8 codec (MXFP8.md, "Stochastic rounding"): the same paths, keys and
+ * refusals, the E4M3 kernels; its own two kinds under BAGUA_CHECK_SCHEDULE. */
+int bagua_centralized_mxfp8_stochastic(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t, int average,
                                        uint64_t seed, uint64_t step, int pieces);
 int bagua_centralized_low_precision_synchronous(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t,
                                                 int average, int method);
@@ -334,7 +341,8 @@ enum {
     BAGUA_BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK = 5, /* bagua_centralized_onebit_error_feedback */
     BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK = 6,  /* bagua_centralized_mxfp4_error_feedback */
     BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC = 7,      /* bagua_centralized_mxfp4_stochastic */
-    BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK = 8   /* bagua_centralized_mxfp8_error_feedback */
+    BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK = 8,  /* bagua_centralized_mxfp8_error_feedback */
+    BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC = 9       /* bagua_centralized_mxfp8_stochastic */
 };
 
 typedef struct bagua_bucket_op {
@@ -356,8 +364,9 @@ typedef struct bagua_bucket_op {
      * BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK: the two residuals travel in
      * ef_worker_carry and ef_server_carry; the two scale fields must be absent. */
     bagua_tensor_t ef_worker_carry, ef_worker_scales, ef_server_carry, ef_server_scale;
-    /* BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC: the seed of the op's rounding (compression
-     * must be BAGUA_COMPRESSION_MXFP4, intranode and the four state tensors absent).  The
+    /* BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC and BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC:
+     * the seed of the op's rounding (compression must be the kind's own codec,
+     * BAGUA_COMPRESSION_MXFP4 / _MXFP8, intranode and the four state tensors absent).  The
      * bucket counts the op's executions: the first after the append runs step 0, the next step
      * 1, ...; an execution replayed from a captured graph repeats the step it was captured with.
      * Appended last: bagua_bucket_append_op reads the other kinds up to this field only. */

@@ -373,6 +373,27 @@ int bagua_mxfp4_reduce_requantize_sr_range(int dtype, const uint8_t* input, size
                                            int target_chunk, int block_begin, int block_end, uint64_t key,
                                            bagua_stream_t stream);
 
+/* MXFP8 with stochastic rounding (MXFP8.md, "Stochastic rounding"): the same for the E4M3
+ * block.  Keys and words are the 4-bit codec's (bagua_mxfp4_sr_key, bagua_mxfp4_sr_word);
+ * scale bytes are the plain MXFP8 encode's, and no element byte has magnitude 0x7F.
+ * Arguments, status codes and refusals are the MXFP4 namesakes' (BAGUA_ERR_UNSUPPORTED past 16
+ * segments), alignment rules the plain MXFP8 entries' (16-B output; the middle step's input
+ * 16-B).  BAGUA_MXFP8_HWCVT selects the conversion as in the plain kernels; both give the
+ * same bytes. */
+int bagua_mxfp8_compress_sr(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                            uint8_t* output, size_t output_bytes, int target_chunk, uint64_t key,
+                            bagua_stream_t stream);
+int bagua_mxfp8_compress_sr_range(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                                  uint8_t* output, size_t output_bytes, int block_begin, int block_end, uint64_t key,
+                                  bagua_stream_t stream);
+int bagua_mxfp8_reduce_requantize_sr(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                     int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                     int target_chunk, uint64_t key, bagua_stream_t stream);
+int bagua_mxfp8_reduce_requantize_sr_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                           int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                           int target_chunk, int block_begin, int block_end, uint64_t key,
+                                           bagua_stream_t stream);
+
 /* The decentralized ring op (decentralized_low_precision_synchronous.rs:45-64,126-151) with the
  * MXFP4 codec, fused (MXFP4.md, "Ring op").  The segment is the num_chunks = 1 layout,
  * bagua_mxfp4_compressed_bytes(num_elem, 1) bytes.  Byte for byte what the elementwise

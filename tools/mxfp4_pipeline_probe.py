@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-rank kernels of the pipelined MXFP4 op (comm_ops.cpp centralized_pipelined_mxfp4) on
+"""Per-rank kernels of the pipelined MXFP4 op (comm_ops.cpp centralized_pipelined_mx) on
 one GPU without the exchange, timed one by one with the kernels' own HIP events
 (bagua_time_next_kernels): 1 GiB of fp32 and 2^28 bf16 elements, p = 2, 4 and 8, with 4
 uniform, 4 tapered and 8 tapered pieces, interleaved in every repetition with the unpieced
