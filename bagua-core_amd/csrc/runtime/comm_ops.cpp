@@ -150,7 +150,7 @@ int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_
 enum { kOpCentralized = 1, kOpCentralizedUnfused, kOpCentralizedPipelined, kOpOneBitPipelined, kOpRing,
        kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback, kOpMxfp4Pipelined, kOpMxfp4Stochastic,
        kOpMxfp4StochasticPipelined, kOpMxfp8Pipelined, kOpMxfp8ErrorFeedback, kOpMxfp8Stochastic,
-       kOpMxfp8StochasticPipelined };
+       kOpMxfp8StochasticPipelined, kOpMxfp6Pipelined };
 
 // The alltoall of the unpieced ops: slot j of recv <- rank j's segment `rank`.  One rank
 // receives its own bytes by a device copy (RCCL's single-rank copy kernel was slower: 1 GiB
@@ -225,8 +225,26 @@ const MxCodec kMxfp8{BAGUA_COMPRESSION_MXFP8,
                      bagua_mxfp8_reduce_requantize_sr,
                      bagua_mxfp8_compress_sr_range,
                      bagua_mxfp8_reduce_requantize_sr_range};
+// MXFP6 (MXFP6.md) has no stochastic rounding: no keyed entry and no stochastic op kind, and no
+// entry point passes keys with it
+const MxCodec kMxfp6{BAGUA_COMPRESSION_MXFP6,
+                     kOpMxfp6Pipelined,
+                     0,
+                     0,
+                     bagua_mxfp6_compress_range,
+                     bagua_mxfp6_reduce_requantize_range,
+                     bagua_mxfp6_decompress_range,
+                     mxfp6_pieces,
+                     bagua_mxfp6_reduce_requantize,
+                     nullptr,
+                     nullptr,
+                     nullptr,
+                     nullptr};
 const MxCodec* mx_codec(int method) {
-    return method == BAGUA_COMPRESSION_MXFP4 ? &kMxfp4 : method == BAGUA_COMPRESSION_MXFP8 ? &kMxfp8 : nullptr;
+    return method == BAGUA_COMPRESSION_MXFP4   ? &kMxfp4
+           : method == BAGUA_COMPRESSION_MXFP8 ? &kMxfp8
+           : method == BAGUA_COMPRESSION_MXFP6 ? &kMxfp6
+                                               : nullptr;
 }
 
 // bagua_tensor_compress_into for a block codec under a key; cs fits an int (plan, below)
@@ -354,7 +372,7 @@ int centralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int averag
         if (rc == BAGUA_OK) done = true;
         else if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);
     } else if (fused && mx && t->num_elem == t->num_elem_allocated) {
-        // MXFP4 / MXFP8: one kernel, no workspace; the reduced chunk is not stored (step 5 rewrites every element)
+        // MXFP4 / MXFP8 / MXFP6: one kernel, no workspace; the reduced chunk is not stored (step 5 rewrites every element)
         rc = sr ? mx->reduce_requantize_sr(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, average,
                                            send.as<uint8_t>(), k.S, k.rank, sr->server, (void*)(uintptr_t)s)
                 : mx->reduce_requantize(t->dtype, recv.as<uint8_t>(), k.S, (int)k.cs, k.p, nullptr, average,
@@ -1026,6 +1044,7 @@ int bagua_centralized_low_precision_pipelined(BaguaSingleCommunicatorC* c, const
     if (method == BAGUA_COMPRESSION_ONEBIT) return centralized_pipelined_onebit(c, t, average, pieces);
     if (method == BAGUA_COMPRESSION_MXFP4) return centralized_pipelined_mx(c, t, average, pieces, kMxfp4);
     if (method == BAGUA_COMPRESSION_MXFP8) return centralized_pipelined_mx(c, t, average, pieces, kMxfp8);
+    if (method == BAGUA_COMPRESSION_MXFP6) return centralized_pipelined_mx(c, t, average, pieces, kMxfp6);
     if (method != BAGUA_COMPRESSION_MINMAX_UINT8) return centralized(c, t, average, method, true);
     return centralized_pipelined(c, t, average, pieces);
 }

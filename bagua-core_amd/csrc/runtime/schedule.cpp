@@ -119,6 +119,12 @@ int mxfp8_pieces(const Chunking& k, int sched, std::vector<Piece>* v) {
     return mx_block_pieces(k, sched, v, bagua_mxfp8_piece_range, 32);
 }
 
+// MXFP6 (MXFP6.md): the same with 24 payload bytes per block, [sbytes + 24 b, sbytes + 24 e); a
+// granule of 128 blocks is 3072 bytes, so the inner edges stay on 32-B lines
+int mxfp6_pieces(const Chunking& k, int sched, std::vector<Piece>* v) {
+    return mx_block_pieces(k, sched, v, bagua_mxfp6_piece_range, 24);
+}
+
 // ---- ring exchange schedule ------------------------------------------------
 // The reference sends the whole compressed bucket straight to both ring peers
 // (decentralized_low_precision_synchronous.rs:98-115).  On a fully connected
@@ -255,12 +261,14 @@ int bagua_centralized_piece_plan(int method, int dtype, int nranks, size_t chunk
     if (method == BAGUA_COMPRESSION_MINMAX_UINT8) k.S = bagua_minmax_u8_compressed_bytes(dtype, cs, nranks);
     else if (method == BAGUA_COMPRESSION_ONEBIT) k.S = bagua_onebit_compressed_bytes(cs, nranks);
     else if (method == BAGUA_COMPRESSION_MXFP4) k.S = bagua_mxfp4_compressed_bytes(cs, nranks);
+    else if (method == BAGUA_COMPRESSION_MXFP6) k.S = bagua_mxfp6_compressed_bytes(cs, nranks);
     else return -BAGUA_ERR_UNSUPPORTED;  // no pieced op, or none this entry describes (MXFP8: MXFP8.md, "Pipelined op")
     if (!k.S) return -BAGUA_ERR_UNSUPPORTED;
     if (k.S % (size_t)k.p) return -BAGUA_ERR_INVALID_ARG;  // the ops refuse it too (alltoall alignment)
     std::vector<Piece> v;
     const int rc = method == BAGUA_COMPRESSION_MINMAX_UINT8 ? minmax_pieces(k, schedule, &v)
                    : method == BAGUA_COMPRESSION_ONEBIT     ? onebit_pieces(k, schedule, &v)
+                   : method == BAGUA_COMPRESSION_MXFP6      ? mxfp6_pieces(k, schedule, &v)
                                                             : mxfp4_pieces(k, schedule, &v);
     if (rc) return -rc;
     if (piece < 0 || (size_t)piece >= v.size()) return -BAGUA_ERR_INVALID_ARG;

@@ -299,6 +299,41 @@ int bagua_mxfp8_reduce_requantize_range(int dtype, const uint8_t* input, size_t 
                                         int num_chunks, int average, uint8_t* output, size_t output_bytes,
                                         int target_chunk, int block_begin, int block_end, bagua_stream_t stream);
 
+/* ======================================================================== */
+/* v2 — MXFP6 block-scaled 6-bit codec (extension; format in MXFP6.md)       */
+/* ======================================================================== */
+/* OCP MXFP6: 32 E2M3 elements under one power-of-two scale byte.  Per chunk: align32(nb)
+ * scale bytes, then align32(24 * nb) payload bytes (element j of a block is bits [6 j, 6 j + 6)
+ * of the block's 24 bytes, read as a little-endian number), nb = ceil(chunk_size / 32); S =
+ * num_chunks * that; all slack is written as zeros.  Single-pass kernels, no workspace.  The
+ * buffers must hold at least S bytes (BAGUA_ERR_INVALID_ARG otherwise).  Alignment: the
+ * output of bagua_mxfp6_compress{,_range} 16 B (payload stored as 4-B / 8-B words); the input
+ * of bagua_mxfp6_decompress{,_range} 8 B (payload loaded as 4-B / 8-B words); input and
+ * output of bagua_mxfp6_reduce_requantize{,_range} 16 B; tensors as their dtype (a tensor
+ * that is not 16-B aligned takes element accesses).  The entries mirror their MXFP8
+ * namesakes above: the same arguments, status codes, piece rule (a granule of 128 blocks;
+ * payload bytes [sbytes + 24 bb, sbytes + 24 be) of each segment) and refusals.
+ * bagua_mxfp6_reduce_requantize is byte for byte bagua_mxfp6_decompress +
+ * bagua_reduce_chunks + bagua_mxfp6_compress(target) on a fully valid tensor; `tensor` may
+ * be NULL (the reduced chunk is not stored); BAGUA_ERR_UNSUPPORTED for num_chunks > 16. */
+size_t bagua_mxfp6_compressed_bytes(int chunk_size, int num_chunks);
+int bagua_mxfp6_compress(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                         uint8_t* output, size_t output_bytes, int target_chunk, bagua_stream_t stream);
+int bagua_mxfp6_decompress(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                           void* output, bagua_stream_t stream);
+int bagua_mxfp6_reduce_requantize(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                                  void* tensor, int average, uint8_t* output, size_t output_bytes, int target_chunk,
+                                  bagua_stream_t stream);
+int bagua_mxfp6_piece_range(int chunk_size, int pieces, int piece, int* block_begin, int* block_end);
+int bagua_mxfp6_compress_range(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                               uint8_t* output, size_t output_bytes, int block_begin, int block_end,
+                               bagua_stream_t stream);
+int bagua_mxfp6_decompress_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size, int num_chunks,
+                                 void* output, int block_begin, int block_end, bagua_stream_t stream);
+int bagua_mxfp6_reduce_requantize_range(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                        int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                        int target_chunk, int block_begin, int block_end, bagua_stream_t stream);
+
 /* MXFP4 with error feedback (MXFP4.md, "Error feedback"): the same wire format, plus
  * caller-owned f32 state, zero before the first step, that carries each step's
  * quantisation error into the next.  The state is the residual itself: worker

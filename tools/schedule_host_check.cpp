@@ -24,19 +24,21 @@ static int fail(const char* what, int a, int b, int c, int d) {
 static size_t segments(int method, int p, int cs) {
     if (method == BAGUA_COMPRESSION_MINMAX_UINT8) return bagua_minmax_u8_compressed_bytes(BAGUA_DTYPE_F32, cs, p);
     if (method == BAGUA_COMPRESSION_ONEBIT) return bagua_onebit_compressed_bytes(cs, p);
+    if (method == BAGUA_COMPRESSION_MXFP6) return bagua_mxfp6_compressed_bytes(cs, p);
     return bagua_mxfp4_compressed_bytes(cs, p);
 }
 
 int main() {
     const int ranks[] = {1, 2, 3, 8, 16};
     const int schedules[] = {1, 2, 3, 4, 7, 3 | BAGUA_PIECES_TAPERED, 5 | BAGUA_PIECES_TAPERED, 8 | BAGUA_PIECES_TAPERED};
-    const std::vector<int> chunks[5] = {{4096},  // methods 0 and 4: no pieced op, refused
+    const std::vector<int> chunks[6] = {{4096},  // methods 0 and 4: no pieced op, refused
                                         {1, 511, 512, 1536, 12345, 40000},
                                         {1, 1023, 1024, 1025, 5000, 12288},
                                         {1, 32, 4095, 4096, 4097, 12288, 40000},
-                                        {4096}};
+                                        {4096},
+                                        {1, 32, 4095, 4096, 4097, 12288, 40000}};  // MXFP6: 24 payload bytes per block
     long calls = 0;
-    for (int method = 0; method <= 4; ++method)
+    for (int method = 0; method <= 5; ++method)
         for (int p : ranks)
             for (int cs : chunks[method])
                 for (int sched : schedules)
