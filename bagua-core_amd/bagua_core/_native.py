@@ -199,6 +199,9 @@ KERNEL_SIGNATURES = {
     "bagua_ring_mix_mxfp8": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "bagua_ring_apply_mxfp8": (_i32, [_i32, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp]),
     "bagua_ring_one_rank_mxfp8": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "bagua_ring_mix_mxfp6": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "bagua_ring_apply_mxfp6": (_i32, [_i32, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "bagua_ring_one_rank_mxfp6": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "bagua_reduce_chunks": (_i32, [_i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "bagua_add_inplace": (_i32, [_i32, _vp, _vp, _i32, _vp]),
     "bagua_addmul_inplace": (_i32, [_i32, _vp, _vp, _i32, _f32, _vp]),

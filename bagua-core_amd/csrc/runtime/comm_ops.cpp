@@ -1123,8 +1123,8 @@ int bagua_centralized_full_precision_synchronous(BaguaSingleCommunicatorC* c, co
     return finish(c, rc);
 }
 
-// The fused ring kernels of a block codec (mxfp4_ring.hip, mxfp8_ring.hip: the same three
-// entries) and the switch that turns them off
+// The fused ring kernels of a block codec (mxfp4_ring.hip, mxfp8_ring.hip, mxfp6_ring.hip: the
+// same three entries) and the switch that turns them off
 struct MxRing {
     const char* fused_env;
     decltype(&bagua_ring_mix_mxfp4) mix;
@@ -1135,6 +1135,8 @@ static const MxRing kMxfp4Ring{"BAGUA_MXFP4_RING_FUSED", bagua_ring_mix_mxfp4, b
                                bagua_ring_one_rank_mxfp4};
 static const MxRing kMxfp8Ring{"BAGUA_MXFP8_RING_FUSED", bagua_ring_mix_mxfp8, bagua_ring_apply_mxfp8,
                                bagua_ring_one_rank_mxfp8};
+static const MxRing kMxfp6Ring{"BAGUA_MXFP6_RING_FUSED", bagua_ring_mix_mxfp6, bagua_ring_apply_mxfp6,
+                               bagua_ring_one_rank_mxfp6};
 
 static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, const bagua_tensor_t* weight,
                          const bagua_tensor_t* left, const bagua_tensor_t* right, int method, bool allow_fused,
@@ -1149,16 +1151,17 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
     const int n = (int)t->num_elem_allocated;
     const size_t S = bagua_compressed_size(method, t->dtype, 1, t->num_elem_allocated);
     if (!S) return BAGUA_ERR_UNSUPPORTED;
-    // fused kernels (csrc/kernels/decentralized.hip, mxfp4_ring.hip, mxfp8_ring.hip) for fully
-    // valid, same-shape MinMax, MXFP4 and MXFP8 buckets; anything else runs the reference's op
-    // sequence.
+    // fused kernels (csrc/kernels/decentralized.hip, mxfp4_ring.hip, mxfp8_ring.hip,
+    // mxfp6_ring.hip) for fully valid, same-shape MinMax, MXFP4, MXFP8 and MXFP6 buckets;
+    // anything else runs the reference's op sequence.
     // The choice (and with it the pipelined exchange schedule) depends only on values equal
     // on every rank; a rank whose tensors are not 16-B aligned runs on aligned copies.
-    // BAGUA_MXFP4_RING_FUSED=0 / BAGUA_MXFP8_RING_FUSED=0 (read per call, A/B): the op sequence
-    // for that block codec.  It changes no byte on the wire and neither codec is ever
-    // pipelined, so ranks need not agree on it.
+    // BAGUA_MXFP4_RING_FUSED=0 / BAGUA_MXFP8_RING_FUSED=0 / BAGUA_MXFP6_RING_FUSED=0 (read per
+    // call, A/B): the op sequence for that block codec.  It changes no byte on the wire and no
+    // block codec is ever pipelined, so ranks need not agree on it.
     const MxRing* mx = method == BAGUA_COMPRESSION_MXFP4   ? &kMxfp4Ring
                        : method == BAGUA_COMPRESSION_MXFP8 ? &kMxfp8Ring
+                       : method == BAGUA_COMPRESSION_MXFP6 ? &kMxfp6Ring
                                                            : nullptr;
     if (mx && env_int(mx->fused_env, 1) == 0) mx = nullptr;
     bool fused = allow_fused && (method == BAGUA_COMPRESSION_MINMAX_UINT8 || mx) &&
@@ -1182,7 +1185,7 @@ static int decentralized(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, c
                              (uint64_t)n, pipelined ? sched | (multipath ? BAGUA_PIECES_MULTIPATH : 0) : 1, 1)))
         return rc;
     if (mx && fused && c->nranks == 1 && env_int("BAGUA_ONE_RANK_FUSED", 1) != 0) {
-        // one rank: one pass over the four tensors, no payload (bagua_ring_one_rank_mxfp4 / _mxfp8)
+        // one rank: one pass over the four tensors, no payload (bagua_ring_one_rank_mxfp4 / _mxfp8 / _mxfp6)
         rc = mx->one_rank(t->dtype, (void*)(uintptr_t)t->ptr, (void*)(uintptr_t)weight->ptr,
                           (void*)(uintptr_t)left->ptr, (void*)(uintptr_t)right->ptr, n, sp);
         if (rc != BAGUA_ERR_UNSUPPORTED) return finish(c, rc);

@@ -467,6 +467,19 @@ int bagua_ring_apply_mxfp8(int dtype, const uint8_t* mine, const uint8_t* from_l
 int bagua_ring_one_rank_mxfp8(int dtype, void* tensor, void* weight, void* left, void* right, int num_elem,
                               bagua_stream_t stream);
 
+/* ... and with the MXFP6 codec (MXFP6.md, "Ring op"): the segment is
+ * bagua_mxfp6_compressed_bytes(num_elem, 1) bytes, the mix encodes as bagua_mxfp6_compress
+ * (num_chunks = 1), both slacks zeroed, and the apply decodes as bagua_mxfp6_decompress would,
+ * scale byte 0xFF included.  Arguments, results, refusals and alignment rules are their MXFP8
+ * namesakes'. */
+int bagua_ring_mix_mxfp6(int dtype, const void* tensor, const void* left, const void* right, const void* weight,
+                         int num_elem, uint8_t* output, size_t output_bytes, bagua_stream_t stream);
+int bagua_ring_apply_mxfp6(int dtype, const uint8_t* mine, const uint8_t* from_left, const uint8_t* from_right,
+                           size_t compressed_bytes, int num_elem, void* tensor, void* weight, void* left, void* right,
+                           bagua_stream_t stream);
+int bagua_ring_one_rank_mxfp6(int dtype, void* tensor, void* weight, void* left, void* right, int num_elem,
+                              bagua_stream_t stream);
+
 /* ======================================================================== */
 /* v2 — chunk reduction and elementwise ops                                  */
 /* ======================================================================== */

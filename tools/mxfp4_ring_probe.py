@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Measurement: the decentralized ring op with a block codec (--codec mxfp4, the default, or
-mxfp8), fused kernels beside the composed op sequence (MXFP4.md / MXFP8.md, "Ring op").
-CODECS holds what differs between the two: the method, the switch that turns the fused kernels
-off (<SWITCH> below) and the prefix of the kernel names (<codec> below).
+"""Measurement: the decentralized ring op with a block codec (--codec mxfp4, the default,
+mxfp8 or mxfp6), fused kernels beside the composed op sequence (MXFP4.md / MXFP8.md / MXFP6.md,
+"Ring op").  CODECS holds what differs between them: the method, the switch that turns the fused
+kernels off (<SWITCH> below), the prefix of the kernel names (<codec> below) and, for mxfp6, the
+yardstick: another codec whose fused kernels run interleaved in the same run.
 
 Two buckets: 2^26 f32 elements (256 MiB) and 2^27 bf16 elements, each with its weight and
 the two peer weights.  The op runs through its normal entry on loopback communicators, at
@@ -18,6 +19,7 @@ same cache state (the tail of the last copy, at most).
          mix_apply  <codec>_ring_mix_kernel + <codec>_ring_apply_kernel (BAGUA_ONE_RANK_FUSED=0)
          composed   <SWITCH>=0: 3 x addmul, encode, 3 x (decode, add)
   p = 2  mix_apply, composed
+  with a yardstick <y>: <y>_one_rank (p = 1) and <y>_mix_apply, the same two variants with its method
 
 The yardstick is the composed sequence in the same run.  Its eleventh step, the clone W = t,
 is a device-to-device copy that the hook does not see, so the composed kernel sum leaves it
@@ -58,12 +60,14 @@ def hip_runtime_version() -> int:
 
 
 # per codec: the method of the op, the switch that turns the fused kernels off, the prefix of
-# the kernel names, the entry that sizes a segment and the default record
+# the kernel names, the entry that sizes a segment, the default record and the yardstick codec
 CODECS = {
     "mxfp4": ("COMPRESSION_MXFP4", "BAGUA_MXFP4_RING_FUSED", "mxfp4", "bagua_mxfp4_compressed_bytes",
-              "r10_mxfp4_ring.json"),
+              "r10_mxfp4_ring.json", None),
     "mxfp8": ("COMPRESSION_MXFP8", "BAGUA_MXFP8_RING_FUSED", "mxfp8", "bagua_mxfp8_compressed_bytes",
-              "r14_mxfp8_ring.json"),
+              "r14_mxfp8_ring.json", None),
+    "mxfp6": ("COMPRESSION_MXFP6", "BAGUA_MXFP6_RING_FUSED", "mxfp6", "bagua_mxfp6_compressed_bytes",
+              "r18_mxfp6_ring.json", "mxfp8"),
 }
 
 
@@ -78,30 +82,35 @@ def kernel_bytes(kernel, prefix, n, esz, S):
 
 
 def variants_of(codec):
-    """variant -> (environment, the kernels it launches, in order)"""
-    _, switch, k, _, _ = CODECS[codec]
+    """variant -> (the codec whose method it runs, environment, the kernels it launches, in order)"""
+    _, switch, k, _, _, yard = CODECS[codec]
     composed = ["binary_kernel"] * 3 + [f"{k}_encode_kernel"] + [f"{k}_decode_kernel", "binary_kernel"] * 3
-    return {"one_rank": ({"BAGUA_ONE_RANK_FUSED": "1"}, [f"{k}_ring_one_rank_kernel"]),
-            "mix_apply": ({"BAGUA_ONE_RANK_FUSED": "0"}, [f"{k}_ring_mix_kernel", f"{k}_ring_apply_kernel"]),
-            "composed": ({switch: "0"}, composed)}
+    tab = {"composed": (codec, {switch: "0"}, composed)}
+    for c, pre in [(codec, "")] + ([(yard, yard + "_")] if yard else []):
+        y = CODECS[c][2]
+        tab[pre + "one_rank"] = (c, {"BAGUA_ONE_RANK_FUSED": "1"}, [f"{y}_ring_one_rank_kernel"])
+        tab[pre + "mix_apply"] = (c, {"BAGUA_ONE_RANK_FUSED": "0"}, [f"{y}_ring_mix_kernel", f"{y}_ring_apply_kernel"])
+    return tab
 
 
 def measure(bc, N, codec, tdtype, esz, n, p, variants, warmup, reps):
     from bagua_core.communicator import loopback_communicators
     dev = torch.device("cuda", 0)
     comms = loopback_communicators(p, 0)
-    vtab, method = variants_of(codec), getattr(N, CODECS[codec][0])
+    vtab, yard = variants_of(codec), CODECS[codec][5]
     gen = torch.Generator(device=dev).manual_seed(11)
     pristine = [[(torch.randn(n, device=dev, generator=gen) * 1e-3).to(tdtype) for _ in range(4)] for _ in range(p)]
     work = [[torch.empty_like(x) for x in rank] for rank in pristine]
     raws = [[bc.BaguaTensorPy(x, f"r{r}.{k}").raw() for k, x in enumerate(work[r])] for r in range(p)]
-    S = getattr(N.K, CODECS[codec][3])(n, 1)
+    seg = {c: getattr(N.K, CODECS[c][3])(n, 1) for c in {vtab[v][0] for v in variants}}  # segment bytes per codec
+    S = seg[codec]
     st0 = torch.cuda.ExternalStream(comms[0].stream_ptr())
-    times = {v: [[] for _ in vtab[v][1]] for v in variants}
+    times = {v: [[] for _ in vtab[v][2]] for v in variants}
     calls = {v: [] for v in variants}
 
     def step(variant, keep):
-        env, kernels = vtab[variant]
+        vc, env, kernels = vtab[variant]
+        method = getattr(N, CODECS[vc][0])
         for r in range(p):
             for x, src in zip(work[r], pristine[r]):
                 x.copy_(src)
@@ -151,8 +160,9 @@ def measure(bc, N, codec, tdtype, esz, n, p, variants, warmup, reps):
     rec = {"elements": n, "ranks": p, "bytes_per_element": esz, "segment_bytes": int(S)}
     for v in variants:
         ks = []
-        for kernel, ts in zip(vtab[v][1], times[v]):
-            med, nbytes = statistics.median(ts), kernel_bytes(kernel, CODECS[codec][2] + "_", n, esz, S)
+        for kernel, ts in zip(vtab[v][2], times[v]):
+            vc = vtab[v][0]
+            med, nbytes = statistics.median(ts), kernel_bytes(kernel, CODECS[vc][2] + "_", n, esz, seg[vc])
             rate = nbytes / (med * 1e-6) / 1e12
             ks.append({"kernel": kernel, "us": round(med, 2), "min_us": round(min(ts), 2), "max_us": round(max(ts), 2),
                        "bytes": int(nbytes), "tb_per_s": round(rate, 3), "roofline_share": round(rate / PEAK_TB_S, 3)})
@@ -160,8 +170,13 @@ def measure(bc, N, codec, tdtype, esz, n, p, variants, warmup, reps):
         if p == 1:  # the whole call, the clone of the composed sequence included
             rec[v]["call_us"] = round(statistics.median(calls[v]), 2)
     for v in variants:
-        if v != "composed":
+        if vtab[v][0] != codec:  # the yardstick's variants: their segment size, no ratio of their own
+            rec[v]["segment_bytes"] = int(seg[vtab[v][0]])
+        elif v != "composed":
             rec[v]["kernel_sum_over_composed"] = round(rec[v]["kernel_sum_us"] / rec["composed"]["kernel_sum_us"], 4)
+            if yard:
+                rec[v][f"kernel_sum_over_{yard}"] = round(rec[v]["kernel_sum_us"] / rec[f"{yard}_{v}"]["kernel_sum_us"],
+                                                          4)
     return rec
 
 
@@ -220,6 +235,10 @@ def main():
            "peak_tb_per_s": PEAK_TB_S, "device": torch.cuda.get_device_name(0),
            "hip_runtime_version": hip_runtime_version(), "torch_hip": torch.version.hip}
     one, two = ("one_rank", "mix_apply", "composed"), ("mix_apply", "composed")
+    yard = CODECS[args.codec][5]
+    if yard:  # the yardstick's fused kernels, interleaved step by step with the rest
+        rec["yardstick"] = yard
+        one, two = one + (f"{yard}_one_rank", f"{yard}_mix_apply"), two + (f"{yard}_mix_apply",)
     for name, tdtype, esz, n in (("f32", torch.float32, 4, 1 << args.log2n_f32),
                                  ("bf16", torch.bfloat16, 2, 1 << args.log2n_bf16)):
         rec[f"{name}_p1"] = measure(bc, N, args.codec, tdtype, esz, n, 1, one, args.warmup, args.reps)
