@@ -10,13 +10,14 @@ from .backend import BaguaCommBackendPy
 from .bucket import BaguaBucketPy
 from .communicator import BaguaSingleCommunicatorPy
 from .tensor import (METHODS, BaguaTensorPy, MXFP4ErrorFeedbackState, MXFP4StochasticRounding,
-                     MXFP8ErrorFeedbackState, MXFP8StochasticRounding, OneBitErrorFeedbackState)
+                     MXFP6ErrorFeedbackState, MXFP8ErrorFeedbackState, MXFP8StochasticRounding,
+                     OneBitErrorFeedbackState)
 
 __version__ = "0.1.0+mi355x"
 
 __all__ = ["BaguaCommBackendPy", "BaguaBucketPy", "BaguaSingleCommunicatorPy", "BaguaTensorPy", "METHODS",
-           "MXFP4ErrorFeedbackState", "MXFP4StochasticRounding", "MXFP8ErrorFeedbackState", "MXFP8StochasticRounding",
-           "OneBitErrorFeedbackState", "show_version"]
+           "MXFP4ErrorFeedbackState", "MXFP4StochasticRounding", "MXFP6ErrorFeedbackState", "MXFP8ErrorFeedbackState",
+           "MXFP8StochasticRounding", "OneBitErrorFeedbackState", "show_version"]
 
 
 def show_version() -> None:

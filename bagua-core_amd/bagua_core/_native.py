@@ -73,6 +73,7 @@ BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK = 6
 BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC = 7
 BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK = 8
 BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC = 9
+BUCKET_OP_CENTRALIZED_MXFP6_ERROR_FEEDBACK = 10
 STATUS_INVALID_ARG = 1
 
 _T = ctypes.POINTER(bagua_tensor_t)
@@ -167,6 +168,9 @@ KERNEL_SIGNATURES = {
     "bagua_mxfp6_compress": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
     "bagua_mxfp6_decompress": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _vp]),
     "bagua_mxfp6_reduce_requantize": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _vp, _sz, _i32, _vp]),
+    "bagua_mxfp6_ef_state_bytes": (_i32, [_i32, _i32, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "bagua_mxfp6_compress_ef": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
+    "bagua_mxfp6_reduce_requantize_ef": (_i32, [_i32, _vp, _sz, _i32, _i32, _i32, _vp, _sz, _i32, _vp, _vp]),
     "bagua_mxfp6_piece_range": (_i32, [_i32, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "bagua_mxfp6_compress_range": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _i32, _vp]),
     "bagua_mxfp6_decompress_range": (_i32, [_i32, _vp, _sz, _i32, _i32, _vp, _i32, _i32, _vp]),
@@ -254,6 +258,7 @@ CORE_SIGNATURES = {
     "bagua_tensor_compress_error_feedback": (_i32, [_T, _i32, _u64, _T, _T, _T]),
     "bagua_tensor_compress_mxfp4_error_feedback": (_i32, [_T, _i32, _u64, _T, _T]),
     "bagua_tensor_compress_mxfp8_error_feedback": (_i32, [_T, _i32, _u64, _T, _T]),
+    "bagua_tensor_compress_mxfp6_error_feedback": (_i32, [_T, _i32, _u64, _T, _T]),
     "bagua_tensor_compress_mxfp4_stochastic": (_i32, [_T, _i32, _u64, _u64, _u64, _T]),
     "bagua_tensor_compress_mxfp8_stochastic": (_i32, [_T, _i32, _u64, _u64, _u64, _T]),
     "bagua_tensor_decompress_from": (_i32, [_T, _i32, _i32, _T, _u64]),
@@ -297,6 +302,7 @@ CORE_SIGNATURES = {
     "bagua_centralized_onebit_error_feedback": (_i32, [_C, _T, _i32, _T, _T, _T, _T, _i32]),
     "bagua_centralized_mxfp4_error_feedback": (_i32, [_C, _T, _i32, _T, _T]),
     "bagua_centralized_mxfp8_error_feedback": (_i32, [_C, _T, _i32, _T, _T]),
+    "bagua_centralized_mxfp6_error_feedback": (_i32, [_C, _T, _i32, _T, _T]),
     "bagua_centralized_mxfp4_stochastic": (_i32, [_C, _T, _i32, _u64, _u64, _i32]),
     "bagua_centralized_mxfp8_stochastic": (_i32, [_C, _T, _i32, _u64, _u64, _i32]),
     "bagua_centralized_full_precision_synchronous": (_i32, [_C, _T, _i32]),

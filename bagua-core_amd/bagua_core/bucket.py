@@ -13,6 +13,7 @@ on the communicator's stream:
   CentralizedMXFP4Stochastic           -> bagua_centralized_mxfp4_stochastic
   CentralizedMXFP8ErrorFeedback        -> bagua_centralized_mxfp8_error_feedback
   CentralizedMXFP8Stochastic           -> bagua_centralized_mxfp8_stochastic
+  CentralizedMXFP6ErrorFeedback        -> bagua_centralized_mxfp6_error_feedback
   CentralizedFullPrecisionSynchronous  -> bagua_centralized_full_precision_synchronous
   DecentralizedLowPrecisionSynchronous -> bagua_decentralized_low_precision_synchronous
   PythonOp                             -> a ctypes callback (python_ffi_op.rs)
@@ -32,7 +33,7 @@ from typing import Callable, Optional
 from . import _native as N
 from .communicator import BaguaSingleCommunicatorPy
 from .tensor import (_DTYPES, BaguaTensorPy, MXFP4ErrorFeedbackState, MXFP4StochasticRounding,
-                     MXFP8ErrorFeedbackState, MXFP8StochasticRounding, OneBitErrorFeedbackState, compression_code)
+                     MXFP6ErrorFeedbackState, MXFP8ErrorFeedbackState, MXFP8StochasticRounding, OneBitErrorFeedbackState, compression_code)
 
 CALLBACK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_char_p)
 
@@ -138,6 +139,23 @@ class CentralizedMXFP8Stochastic:
                                       comm=_handle(self.communicator), sr_seed=self.rounding.seed)
 
 
+@dataclass
+class CentralizedMXFP6ErrorFeedback:
+    """the "MXFP6" centralized op carrying its quantisation error from step to step in
+    `state` (kept alive with the op); the residuals travel in the two carry fields"""
+    communicator: BaguaSingleCommunicatorPy
+    average: bool
+    state: MXFP6ErrorFeedbackState
+    compression: str = "MXFP6"
+
+    def native(self) -> N.bagua_bucket_op_t:
+        st = self.state
+        return N.bagua_bucket_op_t(kind=N.BUCKET_OP_CENTRALIZED_MXFP6_ERROR_FEEDBACK, average=int(self.average),
+                                   compression=compression_code(self.compression), fused=1,
+                                   comm=_handle(self.communicator), ef_worker_carry=st._raw(st.worker_residual),
+                                   ef_server_carry=st._raw(st.server_residual))
+
+
 # the rounding class of each codec that has stochastic rounding, and the op it appends
 _SR_CODECS = {"MXFP4": (MXFP4StochasticRounding, CentralizedMXFP4Stochastic),
               "MXFP8": (MXFP8StochasticRounding, CentralizedMXFP8Stochastic)}
@@ -146,7 +164,8 @@ _SR_ROUNDINGS = tuple(r for r, _ in _SR_CODECS.values())
 # the state class of each codec that has error feedback, and the op it appends
 _EF_CODECS = {"OneBitSignScale": (OneBitErrorFeedbackState, CentralizedOneBitErrorFeedback),
               "MXFP4": (MXFP4ErrorFeedbackState, CentralizedMXFP4ErrorFeedback),
-              "MXFP8": (MXFP8ErrorFeedbackState, CentralizedMXFP8ErrorFeedback)}
+              "MXFP8": (MXFP8ErrorFeedbackState, CentralizedMXFP8ErrorFeedback),
+              "MXFP6": (MXFP6ErrorFeedbackState, CentralizedMXFP6ErrorFeedback)}
 _EF_STATES = tuple(state_cls for state_cls, _ in _EF_CODECS.values())
 
 
@@ -274,7 +293,7 @@ class BaguaBucketPy:
         """error_feedback (keyword; not hierarchical): the state that carries the op's
         quantisation error from one execution to the next -- a OneBitErrorFeedbackState with
         "OneBitSignScale", an MXFP4ErrorFeedbackState with "MXFP4", an MXFP8ErrorFeedbackState
-        with "MXFP8".
+        with "MXFP8", an MXFP6ErrorFeedbackState with "MXFP6".
 
         stochastic_rounding (keyword; not hierarchical, not together with error_feedback): an
         MXFP4StochasticRounding with "MXFP4", an MXFP8StochasticRounding with "MXFP8" (the other
@@ -318,7 +337,7 @@ class BaguaBucketPy:
 
     def _append_error_feedback(self, comm, hierarchical, average, compression, state) -> None:
         if compression not in _EF_CODECS:
-            raise NotImplementedError(f"error feedback exists for the OneBitSignScale, MXFP4 and MXFP8 codecs only, "
+            raise NotImplementedError(f"error feedback exists for the OneBitSignScale, MXFP4, MXFP8 and MXFP6 codecs only, "
                                       f"not for compression={compression!r}")
         state_cls, op_cls = _EF_CODECS[compression]
         if isinstance(state, _EF_STATES) and not isinstance(state, state_cls):

@@ -179,12 +179,15 @@ class BaguaTensorPy:
     def compress_with_error_feedback(self, n_chunks: int, state) -> "BaguaTensorPy":
         """compress(codec, n_chunks, -1) of this step's compensated values, the codec being the
         one `state` belongs to: a OneBitErrorFeedbackState ("OneBitSignScale"), an
-        MXFP4ErrorFeedbackState ("MXFP4", MXFP4.md) or an MXFP8ErrorFeedbackState ("MXFP8",
-        MXFP8.md).  The worker half of `state` is read and updated in place; the result is the
-        U8 buffer, owned like compress()'s."""
-        if not isinstance(state, (OneBitErrorFeedbackState, MXFP4ErrorFeedbackState, MXFP8ErrorFeedbackState)):
-            raise TypeError("state must be a OneBitErrorFeedbackState, an MXFP4ErrorFeedbackState or an "
-                            "MXFP8ErrorFeedbackState")
+        MXFP4ErrorFeedbackState ("MXFP4", MXFP4.md), an MXFP8ErrorFeedbackState ("MXFP8",
+        MXFP8.md) or an MXFP6ErrorFeedbackState ("MXFP6", MXFP6.md).  The worker half of `state`
+        is read and updated in place; the result is the U8 buffer, owned like compress()'s."""
+        mx_entries = {MXFP4ErrorFeedbackState: "bagua_tensor_compress_mxfp4_error_feedback",
+                      MXFP8ErrorFeedbackState: "bagua_tensor_compress_mxfp8_error_feedback",
+                      MXFP6ErrorFeedbackState: "bagua_tensor_compress_mxfp6_error_feedback"}
+        if not isinstance(state, (OneBitErrorFeedbackState, *mx_entries)):
+            raise TypeError("state must be a OneBitErrorFeedbackState, an MXFP4ErrorFeedbackState, an "
+                            "MXFP8ErrorFeedbackState or an MXFP6ErrorFeedbackState")
         src = self.raw()
         if n_chunks <= 0 or src.num_elem_allocated % n_chunks != 0:
             raise RuntimeError("compression tensor size % n_chunks must be 0")
@@ -194,9 +197,8 @@ class BaguaTensorPy:
                                f"device {src.device_id}")
         out = N.bagua_tensor_t()
         stream = current_stream_ptr(src.device_id)
-        if isinstance(state, (MXFP4ErrorFeedbackState, MXFP8ErrorFeedbackState)):
-            entry = (N.C.bagua_tensor_compress_mxfp4_error_feedback if isinstance(state, MXFP4ErrorFeedbackState)
-                     else N.C.bagua_tensor_compress_mxfp8_error_feedback)
+        if not isinstance(state, OneBitErrorFeedbackState):
+            entry = getattr(N.C, next(name for cls, name in mx_entries.items() if isinstance(state, cls)))
             residual = state._raw(state.worker_residual)
             rc = entry(ctypes.byref(src), n_chunks, stream, ctypes.byref(residual), ctypes.byref(out))
         else:
@@ -421,4 +423,41 @@ class MXFP8ErrorFeedbackState:
 
     def __repr__(self) -> str:
         return (f"MXFP8ErrorFeedbackState(num_elements={self.num_elements}, nranks={self.nranks}, "
+                f"device_id={self.device_id})")
+
+
+class MXFP6ErrorFeedbackState:
+    """The state of the MXFP6 codec's error feedback for one bucket (MXFP6.md, "Error
+    feedback"): two zero-initialised float32 device tensors, ordinary torch tensors the caller
+    may checkpoint and restore.
+
+      worker_residual[num_elements]            what this rank encodes
+      server_residual[num_elements / nranks]   the own chunk it re-encodes
+
+    The residual is the compensated value minus what the receiver decodes; zero means "no
+    error carried".  A class of its own: a state belongs to one codec."""
+
+    def __init__(self, num_elements: int, nranks: int, device_id: int):
+        if nranks <= 0 or num_elements <= 0 or num_elements % nranks != 0:
+            raise ValueError(f"num_elements ({num_elements}) must be a positive multiple of nranks ({nranks})")
+        self.num_elements, self.nranks, self.device_id = int(num_elements), int(nranks), int(device_id)
+        dev = torch.device("cuda", self.device_id)
+        self.worker_residual = torch.zeros(self.num_elements, dtype=torch.float32, device=dev)
+        self.server_residual = torch.zeros(self.num_elements // self.nranks, dtype=torch.float32, device=dev)
+        self._op = None  # the bucket op using this state (one state, one op)
+
+    def tensors(self) -> tuple:
+        return self.worker_residual, self.server_residual
+
+    def zero_(self) -> "MXFP6ErrorFeedbackState":
+        for t in self.tensors():
+            t.zero_()
+        return self
+
+    def _raw(self, t: torch.Tensor) -> N.bagua_tensor_t:
+        n = t.numel()
+        return N.bagua_tensor_t(t.data_ptr(), n, n, N.DTYPE_F32, self.device_id)
+
+    def __repr__(self) -> str:
+        return (f"MXFP6ErrorFeedbackState(num_elements={self.num_elements}, nranks={self.nranks}, "
                 f"device_id={self.device_id})")

@@ -104,4 +104,29 @@ MX_HD void mx6_encode_block(const float (&x)[kMxBlock], float maxf, uint32_t& by
     for (int e = 0; e < kMxBlock; ++e) mx6_put_code(w, 6 * e, mx6_quant(mx_clamp(x[e], maxf), inv));
 }
 
+// ---- error feedback (MXFP6.md, "Error feedback") -----------------------------------
+// MXFP4's rule (mx_encode_block_ef) with the E2M3 block encode and decode: the compensated
+// value mx_ef_sum and the residual against the decode as T stores it, mx_ef_residual<K>, are
+// mxfp4_common.hpp's.  A decode in T's normal range is exact in T (a 4-bit significand), so
+// mx_as_stored rounds only among the denormals of f16 and bf16.
+// K: 0 f32, 1 f16, 2 bf16.  x[32] as f32 and the residual e[32] -> scale byte, payload words and the new residual
+// (all +0 for a NaN block: the state is reset, not poisoned).
+template <int K>
+MX_HD void mx6_encode_block_ef(const float (&x)[kMxBlock], float (&e)[kMxBlock], float maxf, uint32_t& byte,
+                               uint32_t (&w)[kMx6BlockWords]) {
+    float v[kMxBlock];
+#pragma unroll
+    for (int i = 0; i < kMxBlock; ++i) v[i] = mx_ef_sum(x[i], e[i]);
+    mx6_encode_block(v, maxf, byte, w);
+    if (byte == kMxNanScale) {
+#pragma unroll
+        for (int i = 0; i < kMxBlock; ++i) e[i] = 0.0f;
+        return;
+    }
+    const float sc = mx6_scale(byte);
+#pragma unroll
+    for (int i = 0; i < kMxBlock; ++i)
+        e[i] = mx_ef_residual<K>(mx_clamp(v[i], maxf), mx6_dequant(mx6_code_at(w, 6 * i), sc, maxf));
+}
+
 }  // namespace bagua

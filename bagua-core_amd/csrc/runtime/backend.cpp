@@ -174,6 +174,9 @@ int run_op(BaguaBucketC* b, size_t index, const bagua_bucket_op_t& op, const bag
         case BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK:
             return bagua_centralized_mxfp8_error_feedback(op.comm, flat, op.average, &op.ef_worker_carry,
                                                           &op.ef_server_carry);
+        case BAGUA_BUCKET_OP_CENTRALIZED_MXFP6_ERROR_FEEDBACK:
+            return bagua_centralized_mxfp6_error_feedback(op.comm, flat, op.average, &op.ef_worker_carry,
+                                                          &op.ef_server_carry);
         case BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC:
             return bagua_centralized_mxfp4_stochastic(op.comm, flat, op.average, op.sr_seed, b->next_step(index), 0);
         case BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC:
@@ -641,7 +644,7 @@ int bagua_bucket_append_op(BaguaBucketC* b, const bagua_bucket_op_t* op) {
     if (op->kind != BAGUA_BUCKET_OP_CALLBACK && !op->comm && !op->intranode) return BAGUA_ERR_INVALID_ARG;
     if (op->intranode && op->intranode->rank == 0 && !op->comm) return BAGUA_ERR_INVALID_ARG;
     if (op->kind < BAGUA_BUCKET_OP_CENTRALIZED_LOW_PRECISION ||
-        op->kind > BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC)
+        op->kind > BAGUA_BUCKET_OP_CENTRALIZED_MXFP6_ERROR_FEEDBACK)
         return BAGUA_ERR_UNSUPPORTED;
     // sr_seed was appended for the stochastic ops: the other kinds are read up to it only, so
     // callers built against the shorter struct stay valid for them
@@ -658,10 +661,12 @@ int bagua_bucket_append_op(BaguaBucketC* b, const bagua_bucket_op_t* op) {
             return BAGUA_ERR_INVALID_ARG;
     }
     if (op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK ||
-        op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK) {
+        op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK ||
+        op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP6_ERROR_FEEDBACK) {
         // the kind's own codec only, no hierarchical mode, both residuals present, no scale tensors
-        const int codec = op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK ? BAGUA_COMPRESSION_MXFP4
-                                                                                       : BAGUA_COMPRESSION_MXFP8;
+        const int codec = op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK   ? BAGUA_COMPRESSION_MXFP4
+                          : op->kind == BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK ? BAGUA_COMPRESSION_MXFP8
+                                                                                         : BAGUA_COMPRESSION_MXFP6;
         if (op->intranode || op->compression != codec) return BAGUA_ERR_UNSUPPORTED;
         if (!op->ef_worker_carry.ptr || !op->ef_server_carry.ptr || op->ef_worker_scales.ptr ||
             op->ef_server_scale.ptr)

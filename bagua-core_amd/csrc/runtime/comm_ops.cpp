@@ -150,7 +150,7 @@ int check_schedule(BaguaSingleCommunicatorC* c, int op, int method, const bagua_
 enum { kOpCentralized = 1, kOpCentralizedUnfused, kOpCentralizedPipelined, kOpOneBitPipelined, kOpRing,
        kOpRingUnfused, kOpRingPipelined, kOpOneBitErrorFeedback, kOpMxfp4ErrorFeedback, kOpMxfp4Pipelined, kOpMxfp4Stochastic,
        kOpMxfp4StochasticPipelined, kOpMxfp8Pipelined, kOpMxfp8ErrorFeedback, kOpMxfp8Stochastic,
-       kOpMxfp8StochasticPipelined, kOpMxfp6Pipelined };
+       kOpMxfp8StochasticPipelined, kOpMxfp6Pipelined, kOpMxfp6ErrorFeedback };
 
 // The alltoall of the unpieced ops: slot j of recv <- rank j's segment `rank`.  One rank
 // receives its own bytes by a device copy (RCCL's single-rank copy kernel was slower: 1 GiB
@@ -921,12 +921,12 @@ int centralized_pipelined_mx(BaguaSingleCommunicatorC* c, const bagua_tensor_t* 
     return finish_both(c, BAGUA_OK);
 }
 
-// The MXFP4 / MXFP8 op with error feedback (MXFP4.md, MXFP8.md): centralized()'s steps for
+// The MXFP4 / MXFP8 / MXFP6 op with error feedback (MXFP4.md, MXFP8.md, MXFP6.md): centralized()'s steps for
 // the codec with its two `_ef` kernels.  The worker residual compensates what this rank
 // encodes for the alltoall, the server residual the own chunk it re-encodes for the
 // allgather; wire format, collectives, segment sizes and the final decode are the plain op's.
 // One stream, no pieces; one rank takes the same path (its own bytes arrive by a device copy).
-// What differs between the two codecs is the table below.
+// What differs between the codecs is the table below.
 struct MxEfCodec {
     int method, op_kind;
     decltype(&bagua_mxfp4_compress_ef) compress_ef;
@@ -936,6 +936,8 @@ const MxEfCodec kMxfp4Ef{BAGUA_COMPRESSION_MXFP4, kOpMxfp4ErrorFeedback, bagua_m
                          bagua_mxfp4_reduce_requantize_ef};
 const MxEfCodec kMxfp8Ef{BAGUA_COMPRESSION_MXFP8, kOpMxfp8ErrorFeedback, bagua_mxfp8_compress_ef,
                          bagua_mxfp8_reduce_requantize_ef};
+const MxEfCodec kMxfp6Ef{BAGUA_COMPRESSION_MXFP6, kOpMxfp6ErrorFeedback, bagua_mxfp6_compress_ef,
+                         bagua_mxfp6_reduce_requantize_ef};
 
 int centralized_mx_ef(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average, float* worker, float* server,
                       const MxEfCodec& mx) {
@@ -1082,6 +1084,12 @@ int bagua_centralized_mxfp8_error_feedback(BaguaSingleCommunicatorC* c, const ba
                                            const bagua_tensor_t* worker_residual,
                                            const bagua_tensor_t* server_residual) {
     return centralized_mx_ef_entry(c, t, average, worker_residual, server_residual, kMxfp8Ef);
+}
+
+int bagua_centralized_mxfp6_error_feedback(BaguaSingleCommunicatorC* c, const bagua_tensor_t* t, int average,
+                                           const bagua_tensor_t* worker_residual,
+                                           const bagua_tensor_t* server_residual) {
+    return centralized_mx_ef_entry(c, t, average, worker_residual, server_residual, kMxfp6Ef);
 }
 
 // the stochastic op of either block codec

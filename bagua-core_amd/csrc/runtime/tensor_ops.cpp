@@ -287,8 +287,8 @@ int bagua_tensor_compress_mxfp8_stochastic(const bagua_tensor_t* t, int n_chunks
                                   bagua_mxfp8_compress_sr);
 }
 
-// the MXFP4 / MXFP8 compress with error-feedback state (bagua_mxfp4_compress_ef /
-// bagua_mxfp8_compress_ef): `residual` (num_elem F32) on the tensor's device, 16-B aligned
+// the MXFP4 / MXFP8 / MXFP6 compress with error-feedback state (bagua_mxfp4_compress_ef and its
+// namesakes): `residual` (num_elem F32) on the tensor's device, 16-B aligned
 static int compress_mx_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
                                       const bagua_tensor_t* residual, bagua_tensor_t* out,
                                       decltype(&bagua_mxfp4_compressed_bytes) compressed_bytes,
@@ -331,6 +331,12 @@ int bagua_tensor_compress_mxfp8_error_feedback(const bagua_tensor_t* t, int n_ch
                                                const bagua_tensor_t* residual, bagua_tensor_t* out) {
     return compress_mx_error_feedback(t, n_chunks, stream, residual, out, bagua_mxfp8_compressed_bytes,
                                       bagua_mxfp8_compress_ef);
+}
+
+int bagua_tensor_compress_mxfp6_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
+                                               const bagua_tensor_t* residual, bagua_tensor_t* out) {
+    return compress_mx_error_feedback(t, n_chunks, stream, residual, out, bagua_mxfp6_compressed_bytes,
+                                      bagua_mxfp6_compress_ef);
 }
 
 int bagua_tensor_decompress_from(const bagua_tensor_t* t, int method, int n_chunks, const bagua_tensor_t* compressed,

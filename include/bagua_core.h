@@ -105,6 +105,9 @@ int bagua_tensor_compress_mxfp4_error_feedback(const bagua_tensor_t* t, int n_ch
 /* the same with the "MXFP8" codec (bagua_mxfp8_compress_ef) */
 int bagua_tensor_compress_mxfp8_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
                                                const bagua_tensor_t* residual, bagua_tensor_t* out);
+/* the same with the "MXFP6" codec (bagua_mxfp6_compress_ef) */
+int bagua_tensor_compress_mxfp6_error_feedback(const bagua_tensor_t* t, int n_chunks, uint64_t stream,
+                                               const bagua_tensor_t* residual, bagua_tensor_t* out);
 /* bagua_tensor_compress with "MXFP4" and stochastic rounding under the key
  * bagua_mxfp4_sr_key(seed, step, 0, 0); bagua_tensor_decompress_from decodes it. */
 int bagua_tensor_compress_mxfp4_stochastic(const bagua_tensor_t* t, int n_chunks, uint64_t stream, uint64_t seed,
@@ -248,6 +251,11 @@ int bagua_centralized_mxfp4_error_feedback(BaguaSingleCommunicatorC* comm, const
 int bagua_centralized_mxfp8_error_feedback(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t, int average,
                                            const bagua_tensor_t* worker_residual,
                                            const bagua_tensor_t* server_residual);
+/* The MXFP6 op with error feedback (MXFP6.md, "Error feedback"): the same with the "MXFP6"
+ * codec and its two `_ef` kernels, again with a schedule kind of its own. */
+int bagua_centralized_mxfp6_error_feedback(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t, int average,
+                                           const bagua_tensor_t* worker_residual,
+                                           const bagua_tensor_t* server_residual);
 /* the reference's unfused sequence, kept for A/B measurement and parity */
 int bagua_centralized_low_precision_synchronous_unfused(BaguaSingleCommunicatorC* comm, const bagua_tensor_t* t,
                                                         int average, int method);
@@ -342,7 +350,8 @@ enum {
     BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK = 6,  /* bagua_centralized_mxfp4_error_feedback */
     BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC = 7,      /* bagua_centralized_mxfp4_stochastic */
     BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK = 8,  /* bagua_centralized_mxfp8_error_feedback */
-    BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC = 9       /* bagua_centralized_mxfp8_stochastic */
+    BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC = 9,      /* bagua_centralized_mxfp8_stochastic */
+    BAGUA_BUCKET_OP_CENTRALIZED_MXFP6_ERROR_FEEDBACK = 10  /* bagua_centralized_mxfp6_error_feedback */
 };
 
 typedef struct bagua_bucket_op {
@@ -360,8 +369,8 @@ typedef struct bagua_bucket_op {
     /* BAGUA_BUCKET_OP_CENTRALIZED_ONEBIT_ERROR_FEEDBACK: the op's state (F32, on the bucket's
      * device, sized for the flattened bucket; see bagua_centralized_onebit_error_feedback).
      * Zeroed = absent, so initialisers written before these fields existed mean what they meant.
-     * BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK and
-     * BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_ERROR_FEEDBACK: the two residuals travel in
+     * BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_ERROR_FEEDBACK, _MXFP8_ERROR_FEEDBACK and
+     * _MXFP6_ERROR_FEEDBACK: the two residuals travel in
      * ef_worker_carry and ef_server_carry; the two scale fields must be absent. */
     bagua_tensor_t ef_worker_carry, ef_worker_scales, ef_server_carry, ef_server_scale;
     /* BAGUA_BUCKET_OP_CENTRALIZED_MXFP4_STOCHASTIC and BAGUA_BUCKET_OP_CENTRALIZED_MXFP8_STOCHASTIC:

@@ -334,6 +334,23 @@ int bagua_mxfp6_reduce_requantize_range(int dtype, const uint8_t* input, size_t 
                                         int num_chunks, int average, uint8_t* output, size_t output_bytes,
                                         int target_chunk, int block_begin, int block_end, bagua_stream_t stream);
 
+/* MXFP6 with error feedback (MXFP6.md, "Error feedback"): MXFP4's rule below with the E2M3
+ * block encode and decode -- the plain MXFP6 wire format, the same f32 state (worker
+ * residual[chunk_size * num_chunks], server residual[chunk_size], zero before the first
+ * step), the same status codes and refusals as their MXFP8 namesakes.  One kernel each, no
+ * workspace.  bagua_mxfp6_compress_ef: target_chunk = -1 only, every chunk fully valid, a
+ * 16-B aligned output.  bagua_mxfp6_reduce_requantize_ef: the residual is checked first, then
+ * what bagua_mxfp6_reduce_requantize checks (16-B aligned input and output); the reduced chunk
+ * is never stored; BAGUA_ERR_UNSUPPORTED for num_chunks > 16: callers then run
+ * bagua_mxfp6_decompress + bagua_reduce_chunks and bagua_mxfp6_compress_ef on the own chunk. */
+int bagua_mxfp6_ef_state_bytes(int chunk_size, int num_chunks, size_t* worker_bytes, size_t* server_bytes);
+int bagua_mxfp6_compress_ef(int dtype, const void* input, int input_num_element, int chunk_size, int num_chunks,
+                            uint8_t* output, size_t output_bytes, int target_chunk, float* residual,
+                            bagua_stream_t stream);
+int bagua_mxfp6_reduce_requantize_ef(int dtype, const uint8_t* input, size_t input_bytes, int chunk_size,
+                                     int num_chunks, int average, uint8_t* output, size_t output_bytes,
+                                     int target_chunk, float* residual, bagua_stream_t stream);
+
 /* MXFP4 with error feedback (MXFP4.md, "Error feedback"): the same wire format, plus
  * caller-owned f32 state, zero before the first step, that carries each step's
  * quantisation error into the next.  The state is the residual itself: worker
