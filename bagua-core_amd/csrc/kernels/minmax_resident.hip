@@ -29,14 +29,18 @@
 // of the chunk stays on chip without scratch (see the comment above that kernel).
 // minmax_resident_encode_kernel_window (the f32 and bf16 default) keeps the order above
 // and loads a last few held rows into the streaming buffers' registers once pass 1 has
-// streamed, so as much stays on chip and the re-read follows the read closely.
+// streamed, so as much stays on chip and the re-read follows the read closely.  Its default
+// rows run the mixed schedule: once the first turns of the re-read are through, the parked and
+// early rows are stored between its turns, under the latency of the tiles in flight, instead
+// of after its last tile (quant_mixed; 1.5-1.8 us of the 256 MiB f32 encode).
 //
 // Layout of this file: the launch arguments and slice geometry; the per-vector and
 // per-chunk pieces (fold_vec, write_extras, sweep_chunk, fold_missing_slices); the shared
 // phases, each written once as a forced-inline template over the caller's register arrays
 // (draw_ticket, park_tag, load_rows, fold_rows, fold_and_park, fold_stream_ascending, publish_partials,
 // exchange_minmax, quant_rows, quant_parked, quant_top_tile, quant_stream_descending /
-// _ascending, finish); the three kernels, each a sequence of those phases in its own order
+// _ascending, quant_stream_turn, quant_on_chip_group, quant_mixed, finish); the three
+// kernels, each a sequence of those phases in its own order
 // with its own scheduling barriers and trace stamps; then the host side: slots, kResCfg,
 // one table of kernel pointers per dtype built from kResCfg, the launch plan and the C ABI.
 //
@@ -680,6 +684,95 @@ __device__ __forceinline__ void quant_stream_ascending(const uint4* v, int64_t s
     }
 }
 
+// One turn of the mixed phase's re-read: `qa` holds tile i and `qb` tile i - 1 (both requested
+// by the caller or by the turn before); each is stored and requested again two tiles further
+// down (clamped, as above), so a turn ENDS with two tiles in flight and whatever follows it
+// runs under their latency.  The same loads and stores as a turn of quant_stream_descending,
+// rotated by one request; i >= 0.
+template <typename T, int BLOCK, int SB, bool NT>
+__device__ __forceinline__ void quant_stream_turn(const uint4* v, int64_t stream0, int64_t i, int t,
+                                                  const QParams& q, uint8_t* vdst, uint4 (&qa)[SB],
+                                                  uint4 (&qb)[SB]) {
+    constexpr int N = Vec<T>::N;
+    constexpr int64_t tile = (int64_t)SB * BLOCK;
+    const int64_t ba = stream0 + i * tile;
+#pragma unroll
+    for (int j = 0; j < SB; ++j) quant_store<T>(qa[j], q, vdst + (ba + j * BLOCK + t) * N);
+    load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 2 ? i - 2 : 0) * tile, t, qa);
+    if (i >= 1) {
+        const int64_t bb = ba - tile;
+#pragma unroll
+        for (int j = 0; j < SB; ++j) quant_store<T>(qb[j], q, vdst + (bb + j * BLOCK + t) * N);
+    }
+    load_tile<SB, BLOCK, NT>(v, stream0 + (i >= 3 ? i - 3 : 0) * tile, t, qb);
+}
+
+// The on-chip rows of a window-order slice in the order the mixed phase stores them: the H
+// parked rows (slice rows [RE, RE + H), from LDS), then the RE early rows (slice rows [0, RE),
+// from `held`), in groups of kMixGroupRows.  Group K, every index static: a dynamic one would
+// send `held` to scratch.  The parked rows of a group are read from LDS back to back.
+constexpr int kMixGroupRows = 4;
+constexpr int mix_groups(int re, int h) { return (re + h + kMixGroupRows - 1) / kMixGroupRows; }
+
+template <typename T, int BLOCK, int RE, int H, int K, int M>
+__device__ __forceinline__ void quant_on_chip_group(const uint4 (&held)[M], const uint4* park, int t,
+                                                    const QParams& q, uint8_t* vd) {
+    constexpr int N = Vec<T>::N;
+    constexpr int S0 = K * kMixGroupRows;
+    uint4 r[kMixGroupRows];
+#pragma unroll
+    for (int j = 0; j < kMixGroupRows; ++j)
+        if (S0 + j < H) r[j] = park[(S0 + j) * BLOCK + t];
+#pragma unroll
+    for (int j = 0; j < kMixGroupRows; ++j) {
+        if (S0 + j < H) quant_store<T>(r[j], q, vd + (int64_t)(RE + S0 + j) * BLOCK * N);
+        else if (S0 + j < H + RE) quant_store<T>(held[S0 + j - H], q, vd + (int64_t)(S0 + j - H) * BLOCK * N);
+    }
+}
+
+// Group K of the mixed phase: first the turns of the re-read that are due before it (a
+// run-time count, `i` is the next turn's top tile), then the group's rows, under the latency
+// of the two tiles the last turn requested.  The first kMixLeadTurns turns go unmixed, before
+// group 0, and the remaining ones are spread evenly over the groups: at the 256 MiB f32 bucket
+// (14 tiles, 7 turns) the encode measured 73.6 us unmixed, 74.5 mixed from the first turn on,
+// 72.9 / 73.0 / 72.3 / 72.1 / 72.7 / 72.5 after 1 / 2 / 3 / 4 / 5 / 6 turns
+// (profiles/resident_mixed_ab.jsonl) -- stores among the re-read's first, freshest tiles cost
+// it more Infinity-Cache hits than they hide latency.  Parked rows before early rows or after
+// them made no difference beyond 0.3 us; groups of 2 rows lost 1.5 us, groups of 8 spill (bf16).
+constexpr int kMixLeadTurns = 4;
+
+template <typename T, int BLOCK, int RE, int H, int SB, bool NT, int K, int M>
+__device__ __forceinline__ void quant_mixed_group(const uint4* v, int64_t stream0, int64_t nfull, int turns,
+                                                  int64_t& i, int t, const QParams& q, uint8_t* vdst,
+                                                  uint8_t* vd, uint4 (&qa)[SB], uint4 (&qb)[SB],
+                                                  const uint4 (&held)[M], const uint4* park) {
+    const int lead = turns < kMixLeadTurns ? turns : kMixLeadTurns;
+    const int due = lead + (turns - lead) * K / mix_groups(RE, H);  // turns before group K
+    const int64_t stop = nfull - 1 - 2 * (int64_t)due;
+    for (; i > stop; i -= 2) quant_stream_turn<T, BLOCK, SB, NT>(v, stream0, i, t, q, vdst, qa, qb);
+    quant_on_chip_group<T, BLOCK, RE, H, K>(held, park, t, q, vd);
+}
+
+// Mixed pass 2 of the window order, for a slice that holds its whole on-chip part and has
+// nfull > 0 full streamed tiles: the work of quant_stream_descending, quant_parked and
+// quant_rows<..., RE, 0, ...> as ONE sequence, so that the on-chip rows' stores, which need
+// nothing from memory, go out while the re-read's loads are in flight instead of after the last
+// of them.  The sequence is unrolled over the groups of on-chip rows (quant_on_chip_group);
+// between two groups the re-read advances by that gap's share of the (nfull + 1) / 2 turns, two
+// tiles a turn, top down.  Fewer turns than groups: the groups after the last turn follow one
+// another; more: a gap takes several turns, and the turns still due after the last group follow
+// it.  `qa` holds the top full tile and `qb` the one below it (clamped), requested by the caller.
+template <typename T, int BLOCK, int RE, int H, int SB, bool NT, int M, int... K>
+__device__ __forceinline__ void quant_mixed(std::integer_sequence<int, K...>, const uint4* v, int64_t stream0,
+                                            int64_t nfull, int t, const QParams& q, uint8_t* vdst, uint8_t* vd,
+                                            uint4 (&qa)[SB], uint4 (&qb)[SB], const uint4 (&held)[M],
+                                            const uint4* park) {
+    const int turns = (int)((nfull + 1) / 2);
+    int64_t i = nfull - 1;
+    (quant_mixed_group<T, BLOCK, RE, H, SB, NT, K>(v, stream0, nfull, turns, i, t, q, vdst, vd, qa, qb, held, park), ...);
+    for (; i >= 0; i -= 2) quant_stream_turn<T, BLOCK, SB, NT>(v, stream0, i, t, q, vdst, qa, qb);
+}
+
 // ------------------------------------------------------------------------
 // the kernels: one per order of the phases
 // ------------------------------------------------------------------------
@@ -995,9 +1088,17 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_stack(
 // by (the stack order puts the whole on-chip part there), so the re-read finds more of
 // its lines in the Infinity Cache; the register budget is
 // 4 RE + max(streaming buffers, 4 RL) + temporaries.
+//
+// MIX != 0 (the mixed schedule): a slice that holds its whole on-chip part and has a full
+// streamed tile stores its parked and early rows between the turns of the re-read
+// (quant_mixed), so that pass 2 costs closer to the longer of the two than to their sum.
+// The late rows keep their place, and the two top tiles are requested as soon as those are
+// stored, as without it; every other slice takes the sequence above.
 // Trace stamps: 0 entry, 1 pass 1 end, 2 exchange end, 6 late rows stored, 4 streamed
-// rows stored, 5 parked rows stored, 3 end.
-template <typename T, int BLOCK, int RE, int H, int RL, int SB, int NTM>
+// rows stored, 5 parked rows stored, 3 end.  A mixed slice writes 7 once its ragged top tile
+// is stored and both full tiles are requested (the start of the mix; no other slice of this
+// order writes 7), and 4 and 5 together at the end of the mix.
+template <typename T, int BLOCK, int RE, int H, int RL, int SB, int NTM, int MIX>
 __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_window(ResidentArgs a) {
     constexpr int N = Vec<T>::N;
     constexpr bool NT = (NTM & 1) != 0;
@@ -1085,6 +1186,23 @@ __global__ __launch_bounds__(BLOCK, 1) void minmax_resident_encode_kernel_window
     trace_stamp(a, g, 6);
     // the two top streamed tiles (the ragged one, then the top full one) are requested now
     // (buffers of their own: pass 1's would count as live across the exchange)
+    if constexpr (MIX != 0) {
+        if (whole && nfull > 0) {
+            uint4 qa[SB], qb[SB];
+            if (v1 > top) load_rows<SB, 0, BLOCK, NT>(v, top, vl, t, qb);
+            load_tile<SB, BLOCK, NT>(v, stream0 + (nfull - 1) * tile, t, qa);
+            if (v1 > top) quant_top_tile<T, BLOCK, SB>(qb, top, v1, t, q, vdst);
+            load_tile<SB, BLOCK, NT>(v, stream0 + (nfull >= 2 ? nfull - 2 : 0) * tile, t, qb);
+            trace_stamp(a, g, 7);
+            quant_mixed<T, BLOCK, RE, H, SB, NT>(std::make_integer_sequence<int, mix_groups(RE, H)>{}, v, stream0,
+                                                 nfull, t, q, vdst, vd, qa, qb, held, park);
+            __builtin_amdgcn_sched_barrier(0);
+            trace_stamp(a, g, 4);
+            trace_stamp(a, g, 5);
+            finish(a, g, lane_c, t);
+            return;
+        }
+    }
     {
         uint4 qa[SB], qb[SB];
         if (v1 > top) load_rows<SB, 0, BLOCK, NT>(v, top, vl, t, qb);
@@ -1165,6 +1283,7 @@ struct ResidentCfg {
                 // requested before the ticket; bit 2: pass 2 re-reads the streamed tiles bottom-up
     int rl;     // > 0: minmax_resident_encode_kernel_window (window order) with r rows held early and
                 // rl rows held late
+    int mix;    // window order only, != 0: the mixed pass 2 (quant_mixed)
 };
 static constexpr ResidentCfg kResCfg[] = {
     {256, 32, 39, 8, 0},   // 0
@@ -1208,8 +1327,8 @@ static constexpr ResidentCfg kResCfg[] = {
     {512, 44, 19, 4, 3, 0},  // 30: stream-last (as 12) at R = 44, SB = 4: the window rows' control
     // window order (minmax_resident_encode_kernel_window): r rows held early, rl rows held late in
     // the streaming buffers' registers; non-temporal as in 12
-    {512, 44, 19, 4, 3, 0, 8},   // 31: 52 rows in VGPRs (f32 and f16 spill: not candidates there)
-    {512, 40, 19, 4, 3, 0, 12},  // 32: 52 rows in VGPRs without scratch for f32 and bf16
+    {512, 44, 19, 4, 3, 0, 8, 1},   // 31: 52 rows in VGPRs (f32 and f16 spill: not candidates there); mixed pass 2
+    {512, 40, 19, 4, 3, 0, 12, 1},  // 32: 52 rows in VGPRs without scratch for f32 and bf16; mixed pass 2
 };
 constexpr int kResNumCfg = (int)(sizeof(kResCfg) / sizeof(kResCfg[0]));
 static_assert(kResCfg[29].rl == 0 && kResCfg[31].rl == 8 && kResCfg[32].rl == 12, "row numbers are named by BAGUA_RESIDENT_CFG and the tests");
@@ -1246,7 +1365,7 @@ template <typename T, int CFG>
 static ResidentKernel resident_kernel_ptr() {
     constexpr ResidentCfg c = kResCfg[CFG];
     if constexpr (c.rl != 0)
-        return &minmax_resident_encode_kernel_window<T, c.block, c.r, c.h, c.rl, c.sb, c.ntm>;
+        return &minmax_resident_encode_kernel_window<T, c.block, c.r, c.h, c.rl, c.sb, c.ntm, c.mix>;
     else if constexpr (c.stack != 0)
         return &minmax_resident_encode_kernel_stack<T, c.block, c.r, c.h, c.sb, c.ntm, (c.stack & 2) != 0,
                                                     (c.stack & 4) != 0>;

@@ -47,6 +47,7 @@ def main():
     for cfg in [int(c) for c in a.cfgs.split(",")]:
         os.environ["BAGUA_RESIDENT_CFG"] = str(cfg)
         assert K.bagua_minmax_u8_resident_path(0, x.data_ptr(), n, n, 1, comp.data_ptr(), S, -1, sp) == 1
+        tr.zero_()  # stamp 7 is written by some schedules only: none left over from the row before
         rows = []
         for r in range(a.runs + 2):
             K.bagua_minmax_u8_resident_trace(tr.data_ptr() if r >= 2 else None)
@@ -57,7 +58,9 @@ def main():
                 N.check(K.bagua_minmax_u8_decompress(0, comp.data_ptr(), S, n, 1, y.data_ptr(), sp), "decompress")
             if r >= 2:
                 torch.cuda.synchronize()
-                t = tr.cpu().numpy().reshape(cus, 8).astype(np.float64) * (1e3 / khz)  # us
+                raw = tr.cpu().numpy().reshape(cus, 8)
+                stamped7 = bool((raw[:, 7] != 0).all())
+                t = raw.astype(np.float64) * (1e3 / khz)  # us
                 t -= t[:, 0].min()
                 rows.append(t)
         t = np.stack(rows)  # runs x wg x 8
@@ -71,7 +74,17 @@ def main():
         window = order.value == 2
         # stack-order rows run pass 2 as held rows (stamp 6), parked rows (stamp 7), streamed part (end);
         # window-order rows as late rows (stamp 6), streamed part (stamp 4), parked rows (stamp 5), early rows
-        if window:
+        # a window-order row with the mixed schedule (every workgroup wrote stamp 7, the start of the mix:
+        # ragged top tile stored, two full tiles requested): the streamed, parked and early rows are one
+        # phase, from stamp 6 to stamps 4 and 5, which fall together at its end.  The stamps are thread 0's:
+        # pass2_mixed_us is its wave's progress, as the unmixed rows' phases are; pass2_mixed_all_waves_us
+        # runs to stamp 3, behind the closing barrier
+        mixed = window and stamped7
+        if mixed:
+            p2 = {"pass2_late_us": t[:, :, 6] - t[:, :, 2], "pass2_mixed_us": t[:, :, 4] - t[:, :, 6],
+                  "pass2_mixed_after_top_tile_us": t[:, :, 4] - t[:, :, 7],
+                  "pass2_mixed_all_waves_us": t[:, :, 3] - t[:, :, 6]}
+        elif window:
             p2 = {"pass2_late_us": t[:, :, 6] - t[:, :, 2], "pass2_stream_us": t[:, :, 4] - t[:, :, 6],
                   "pass2_lds_us": t[:, :, 5] - t[:, :, 4], "pass2_regs_us": t[:, :, 3] - t[:, :, 5]}
         elif stack:
@@ -98,7 +111,9 @@ def main():
             **{k: float(np.median(v)) for k, v in p2.items()},
             "end_max_us": float(np.median(t[:, :, 3].max(axis=1))),
         }
-        if reread_mb > 0:
+        if mixed:
+            out["schedule"] = "mixed"
+        if reread_mb > 0 and "pass2_stream_us" in out:
             out["pass2_stream_us_per_100mb"] = round(out["pass2_stream_us"] / reread_mb * 100, 2)
         print(json.dumps(out), flush=True)
 
