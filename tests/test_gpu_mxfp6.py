@@ -10,7 +10,7 @@ decode lane own 16-B vectors of T (4 f32 / 8 16-bit elements) and work in groups
 4096 / 8192 elements per iteration; a middle-step lane owns one block of 32 and its workgroup
 8192 elements.  BAGUA_TUNE_MX6_*_BLOCKS=2 caps the grid at two workgroups, which puts the start
 of the second grid-stride iteration at twice what one workgroup covers.  One, two, three and four
-blocks leave 24, 16, 8 and 0 bytes of payload slack."""
+blocks leave 8, 16, 24 and 0 bytes of payload slack."""
 import ctypes
 
 import numpy as np

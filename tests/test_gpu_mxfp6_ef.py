@@ -26,7 +26,7 @@ DTYPES = [F32, F16, BF16]
 OK, INVALID_ARG, UNSUPPORTED = 0, 1, 4
 TILE = 2048  # elements of the worker step's wave tile: 8 rows of 256 f32, 4 rows of 512 f16 / bf16
 # one element, the block's and the tile's edges, three tiles and a ragged third block; the block counts
-# 1, 2, 4, 5, 64, 65 and 195 leave every payload slack: 24, 16, 8 and 0 bytes
+# 1, 2, 4, 5, 64, 65 and 195 leave every payload slack: 8, 16, 24 and 0 bytes (nb mod 4 = 1, 2, 3, 0)
 SIZES = [1, 31, 32, 33, 127, 128, 129, TILE - 1, TILE, TILE + 1, 3 * TILE + 69]
 
 
@@ -113,14 +113,10 @@ def test_hostile_inputs(bc, dtype):
 
 # ------------------------------------------------------------ middle step ----
 # p = 2, 5, 16: one per BY (2, 4, 8), 5 with a partly filled second round of the tree
-@pytest.mark.parametrize("average", [1, 0])
-@pytest.mark.parametrize("p", [2, 5, 16])
-@pytest.mark.parametrize("dtype", DTYPES)
-def test_middle_step(bc, dtype, p, average):
+def middle_steps(bc, dtype, p, average, sizes):
     """three steps against middle_ef; step 1 takes the plain middle step's hostile segments: a NaN block in
-    segment 0 (its residuals reset) and, on f16, a sum that leaves the range (clamped).  cs = 33: two blocks,
-    the second ragged, a residual that is only 4-B aligned; 8193 + 64: two workgroups, 259 blocks"""
-    for cs in (33, 8193 + 64):
+    segment 0 (its residuals reset) and, on f16, a sum that leaves the range (clamped)"""
+    for cs in sizes:
         rng = np.random.default_rng(100 * dtype + 7 * p + cs)
         target, seg = p // 2, R.segment_bytes(cs)
         res = torch.zeros(cs + 1, dtype=torch.float32, device="cuda")[1 if cs == 33 else 0:][:cs]
@@ -141,6 +137,28 @@ def test_middle_step(bc, dtype, p, average):
             if step == 1:  # received() plants its NaN at element 37 of the p * cs
                 b = 37 % cs // 32
                 assert want[target * seg + b] == 0xFF and not ref[32 * b:32 * b + 32].view(np.uint32).any()
+
+
+@pytest.mark.parametrize("average", [1, 0])
+@pytest.mark.parametrize("p", [2, 5, 16])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_middle_step(bc, dtype, p, average):
+    """cs = 33: two blocks, the second ragged, a residual that is only 4-B aligned; 8193 + 64: two workgroups,
+    259 blocks"""
+    middle_steps(bc, dtype, p, average, (33, 8193 + 64))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_one_workgroup_walks_the_grid_stride_loops(bc, dtype, monkeypatch):
+    """the grid caps at one workgroup: ten wave tiles (the last ragged) for the four waves of the worker step,
+    259 blocks for the 256 lanes of the middle step, so both loops take a second turn"""
+    monkeypatch.setenv("BAGUA_TUNE_MX6_ENCODE_BLOCKS", "1")
+    monkeypatch.setenv("BAGUA_TUNE_MX6_MIDDLE_BLOCKS", "1")
+    cs = 9 * TILE + 69
+    rng = np.random.default_rng(70 + dtype)
+    xs = [step_grads(rng, cs, dtype) for _ in range(3)]
+    assert list(worker_steps(bc, dtype, 1, cs, xs, f"one workgroup cs={cs}"))[-1][1].any()
+    middle_steps(bc, dtype, 5, 1, (8193 + 64,))
 
 
 # ------------------------------------------------- the op on the loopback transport ----
